@@ -20,6 +20,10 @@ summed with reduce-scatter + all-gather over RCCL, chunked so that chunk i commu
 multiplies.
 
 Prints ONE JSON line (rank 0).  The timed region starts with all inputs resident in HBM.
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes what the last timed step
+returned.  --full adds, after the timed steps, the measurements the headline does not need: the CPU baseline with its full-size
+parity check, a sustained-rate run, hipBLASLt on the unpacked weight, the perplexity leg (`ppl_delta`) and the other BASELINE
+configs (`configs`).
 """
 import argparse
 import json
@@ -67,7 +71,13 @@ def parse_args(argv=None):
     ap.add_argument("--single-rank-collectives", action="store_true",
                     help="llama70b_rowparallel on ONE GPU: still create the RCCL group (world size 1) and run the reduce-scatter / all-gather, "
                          "so that the communication code path and its evidence keys can be checked without an 8-GPU node")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out everything --full adds")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: the CPU baseline with full-size parity, the sustained-rate "
+                         "run, hipBLASLt on the unpacked weight, the perplexity leg and the other BASELINE configs (`configs`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/<name>.npy (float32); an output over 64 MB is cut to a "
+                         "fixed, seeded sample of its rows")
     ap.add_argument("--stub", action="store_true",
                     help="CPU-only plumbing check (tests): gloo backend, the step is a no-op; exercises rank start-up, "
                          "barriers, max-over-ranks timing and the JSON line without a GPU")
@@ -159,7 +169,30 @@ def synth_weight(N, K, dev, seed=0):
     return W
 
 
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together, headers included
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: every output (name -> tensor) as <path>/<name>.npy in float32.  An output larger than its share of DUMP_BYTES
+    keeps a sample of its rows (first dimension) drawn by a generator of fixed seed: the same rows on every run with the same
+    arguments, so that two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(outputs) - 4096
+    for name, t in outputs.items():
+        t = t.detach()
+        row_bytes = 4 * (t[0].numel() if t.dim() > 1 else 1)
+        if t.numel() * 4 > share:
+            keep = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:share // row_bytes].sort().values
+            t = t[keep.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def physical_cores():
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:            # a host shared with other jobs caps the threads a process may use
+        return int(omp)
     try:
         import psutil
         n = psutil.cpu_count(logical=False)
@@ -499,7 +532,7 @@ def _clone_packed(P):
 
 
 HBM_PEAK_GBPS = 8000.0        # MI355X_MICROARCH.md: 8 TB/s spec (6.3 achievable)
-# sub-objects of the default line's `configs` (BASELINE.json configs 3, 4, 5 and decode) and of `rowparallel`: the --stub path emits
+# sub-objects of the --full line's `configs` (BASELINE.json configs 3, 4, 5 and decode) and of `rowparallel`: the --stub path emits
 # the same keys, tests/test_host_logic.py pins them
 CONFIG_KEYS = ("w4a8_mx", "w4a8_mx_plain_fp4", "w6a8_mx_plain_fp6", "producers", "w4a8_mxlinear", "kv_quant", "rtn_fakequant_in_dtype", "decode_cold", "rowparallel_70b_1gpu", "m_sweep",
                "layer7b_prefill")
@@ -1027,7 +1060,7 @@ def e2e_main(args, dev):
     t_rtn = time.perf_counter() - t0
     # the same arithmetic on the host cores (oracle, all cores) on ONE 4096 x 4096 layer, scaled to the model
     cpu_rtn = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         threads = O.set_threads(physical_cores())
         rng = np.random.RandomState(0)
@@ -1222,6 +1255,10 @@ def e2e_main(args, dev):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and (args.stub or args.workload == "llama7b_e2e"):
+        raise SystemExit("--dump-outputs: the timed step of --stub / llama7b_e2e returns no output")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launcher: start the ranks before anything here touches torch / HIP
         sys.exit(spawn_ranks(args, argv))
@@ -1267,6 +1304,7 @@ def main(argv=None):
         return stub_main(args, rank, world)
     dev = torch.device("cuda", local_rank if world > 1 else 0)
     torch.cuda.set_device(dev)
+    torch.manual_seed(1 + rank)            # X and the other synthetic inputs: the same on every run with the same arguments
 
     from msq import qlinear
 
@@ -1275,6 +1313,7 @@ def main(argv=None):
             raise SystemExit("llama7b_e2e is a single-GPU workload")
         return e2e_main(args, dev)
     M = args.M
+    full = args.full and not args.no_cpu_baseline          # everything after the headline that it does not need
     rowpar = args.workload == "llama70b_rowparallel"
     if rowpar:
         H, N = 8192, 8192                                  # Llama-2-70B down_proj: K = 28672 split over ranks
@@ -1349,7 +1388,7 @@ def main(argv=None):
     else:
         P = qlinear.pack_weight(W, 8, 8, args.inlier, args.outlier, 2, args.block, layout=args.layout)
         X = torch.randn(M, K, device=dev).to(torch.bfloat16)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and full:
             # full-size parity material for cpu_baseline: the run's own weight, the HIP fake-quant of it and what the packed planes decode to
             from msq import quant as _q
             parity_src = (W.cpu().numpy(), {"hip_fakequant": _q.outlier_fakequant(W, 8, 8, args.inlier, args.outlier, 2, -1, args.block)["out"].cpu().numpy(),
@@ -1392,8 +1431,9 @@ def main(argv=None):
     with _no_gc():
         t0 = time.perf_counter()
         ev0.record()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             step()
+        y_last = step()                                    # kept for --dump-outputs; every other step frees its output as before
         ev1.record()
         if world > 1:
             dist.barrier()
@@ -1404,6 +1444,9 @@ def main(argv=None):
         t = torch.tensor([wall], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"y": y_last})
+    del y_last
 
     # who took part, and where the row-parallel step's time goes: GEMM chunks (events on the compute stream) against the whole
     # step, and the collectives alone on the same buffers -- so that the line itself shows how much communication is exposed
@@ -1446,7 +1489,7 @@ def main(argv=None):
             del rp2, Pr, Xr
     flops_step = 2.0 * M * N * K                            # algorithmic: dequant flops not counted
     sus = None
-    if rank == 0 and world == 1 and rp is None and not args.no_cpu_baseline and (M, H) == (2048, 4096):
+    if rank == 0 and world == 1 and rp is None and full and (M, H) == (2048, 4096):
         try:
             sus = sustained(step, flops_step, PEAK_FP8_TFLOPS if mxw4a8 else PEAK_BF16_TFLOPS)
         except Exception as e:                                     # must never take the bench line down
@@ -1477,7 +1520,7 @@ def main(argv=None):
                      "kernel": _kernel_name(P, M, mxw4a8), "kernel_ms": kern_ms, "achieved_hip_events": achieved, "frac_hip_events": achieved / peak,
                      "flops_per_launch": flops_step},
     }
-    if rank == 0 and world == 1 and rp is None and not mxw4a8 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and rp is None and not mxw4a8 and full:
         # the vendor's dense GEMM on the same shape, same box, same run: hipBLASLt bf16 on the UNPACKED weight (judge, round 5, item 5)
         try:
             import torch
@@ -1517,7 +1560,7 @@ def main(argv=None):
         out["config"]["ranks_seen"] = ranks_seen
     if rowpar_times is not None:
         out["rowparallel"] = rowpar_times
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "llama7b_w4_fused_gemm":
+    if rank == 0 and world == 1 and full and args.workload == "llama7b_w4_fused_gemm":
         import contextlib
         try:
             with contextlib.redirect_stdout(sys.stderr):              # the harness prints progress: keep stdout to ONE JSON line
@@ -1534,7 +1577,7 @@ def main(argv=None):
             except Exception as e:
                 out["configs"] = {"error": repr(e)[:300]}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and full:
         out["cpu_baseline"] = cpu_baseline(M, N, K, args.block, args.inlier, args.outlier, plain_mx=(mxw4a8 and not msqmx),
                                            W_host=parity_src[0] if parity_src else None, gpu_values=parity_src[1] if parity_src else None)
     if rank == 0:
@@ -1582,7 +1625,8 @@ def stub_main(args, rank, world):
                 "scaling": "strong" if rowpar else "weak", "vs_baseline": None, "dtype": "none", "data": "none",
                 "config": {"workload": "stub", "ranks_seen": seen}, "rowparallel": rp_obj}
         if world == 1 and not rowpar:
-            line["configs"] = {k: {"ms": 0.0, "frac": 0.0} for k in CONFIG_KEYS}
+            if args.full:
+                line["configs"] = {k: {"ms": 0.0, "frac": 0.0} for k in CONFIG_KEYS}
             line["ppl_delta"] = None
         _emit_json(json.dumps(line))
     if world > 1:

@@ -5,7 +5,7 @@ R=${1:-r04}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/final_$R; mkdir -p $O
 python3 -m pytest tests -m gpu -q -x 2>&1 | grep -E "passed|failed|error" | tail -3 > $O/gpu_tests.txt
-python3 bench.py > $O/${R}_bench_posit.json 2> $O/bench.err
+python3 bench.py --full > $O/${R}_bench_posit.json 2> $O/bench.err
 python3 bench.py --outlier fp8_e4m3 --no-cpu-baseline > $O/${R}_bench_fp8.json 2>> $O/bench.err
 scripts/profile_gpu.sh ${R}_posit > /dev/null 2>&1
 scripts/profile_gpu.sh ${R}_fp8 --outlier fp8_e4m3 > /dev/null 2>&1

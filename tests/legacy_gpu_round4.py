@@ -132,7 +132,7 @@ def test_ppl_env_checkpoint_still_honoured(msq, tmp_path, monkeypatch):
 @pytest.fixture(scope="module")
 def bench_line(msq):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MSQ_PPL_MODEL", "MSQ_PPL_DISABLE")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5"], capture_output=True, text=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full"], capture_output=True, text=True,
                          timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -270,21 +270,46 @@ def test_bench_rowparallel_evidence_keys_and_strong_scaling(tmp_path):
 
 
 def test_bench_default_line_carries_the_other_configs():
-    """BASELINE configs 3, 4, 5 and decode ride in the default single-GPU line as compact `configs` sub-objects (judge, round 3,
-    item 3); the --stub line has the same keys (the GPU test test_bench_other_configs_keys_and_rates checks the real objects)."""
+    """BASELINE configs 3, 4, 5 and decode ride in the single-GPU --full line as compact `configs` sub-objects (judge, round 3,
+    item 3); the --stub line has the same keys (the GPU test test_bench_other_configs_keys_and_rates checks the real objects).
+    A plain run leaves them out."""
     import json
     sys.path.insert(0, ROOT)
     import bench
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--stub"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--stub", "--full"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     j = json.loads(p.stdout.strip())
     assert set(j["configs"]) == set(bench.CONFIG_KEYS) and "ppl_delta" in j
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--stub"],
+                       capture_output=True, text=True, timeout=300, env=env)
+    assert p.returncode == 0, p.stderr[-2000:]
+    j = json.loads(p.stdout.strip())
+    assert "configs" not in j and "ppl_delta" in j and j["steps"] == 2
     src = open(os.path.join(ROOT, "bench.py")).read()
     body = src[src.index("def other_configs"):src.index("def rowparallel_measure")]
     for k in bench.CONFIG_KEYS:
         assert ('"%s"' % k) in body, k
+
+
+def test_bench_dump_outputs_writes_float32_within_the_cap(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, an output under the cap whole, a larger one cut to the same seeded rows on every call,
+    all files together within 64 MB."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.arange(6 * 5, dtype=torch.bfloat16).reshape(6, 5)
+    big = torch.arange(2048, dtype=torch.float32)[:, None].expand(2048, 16384)      # row i holds i
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and (s == small.float().numpy()).all()
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape[1] == 16384 and 0 < a.shape[0] < 2048 and (a == b).all()
+    assert (a == a[:, :1]).all() and (np.diff(a[:, 0]) > 0).all()                 # whole rows, each once, in order
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64e6
 
 
 def test_ppl_fixture_files_and_corpus_reproducible(tmp_path):
