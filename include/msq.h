@@ -80,10 +80,15 @@ extern "C" {
                             NONE (inlier codes are widened to e4m3 at pack time)                   */
 #define MSQ_PLANE_U8X 6  /* unified e4m3 byte + 1 extension bit per weight (a 4th fraction bit: holds
                             posit<8,1> outliers exactly); the extension plane travels as inl_plane   */
+#define MSQ_PLANE_SEL 7  /* compact (with in_kind FP4): the out plane holds ONE SELECT BIT per weight; the weight's
+                            e2m1 nibble in the inlier plane is scaled by the outlier scale where the bit is set
+                            (outlier formats fp4_e2m1, int2: values on the e2m1 grid themselves)    */
 
 /* packed layouts */
 #define MSQ_LAYOUT_PLANES 0  /* "MSQ-T1": inlier plane + outlier plane + two scales per block          */
 #define MSQ_LAYOUT_UNIFIED 1 /* "MSQ-U1": one 8-bit code plane (+ extension bits) + one scale per 32 k */
+#define MSQ_LAYOUT_COMPACT 2 /* "MSQ-C1": one e2m1 nibble + one select bit per weight + two scales per block (int2 / fp4 inliers with
+                                int2 / fp4 outliers, block 16 or 32): 6.0 / 5.5 bits per weight                  */
 
 int msq_version(void);
 const char* msq_last_error(void);
@@ -211,9 +216,29 @@ int msq_outlier_fakequant(const void* in, void* out, uint8_t* mask, float* e_in,
  * 8.25 (U8) / 9.25 (U8X) bits per weight.  The pack kernel decodes every code exactly as the GEMM will
  * and raises MSQ_STATUS_INEXACT if a group cannot be represented (range of more than ~2^15 inside one
  * group); callers then keep the two-plane layout for that tensor.
+ *
+ * Compact layout ("MSQ-C1", in_kind MSQ_PLANE_FP4 with out_kind MSQ_PLANE_SEL; block 16 or 32): when the outlier format
+ * is itself on the e2m1 grid (fp4_e2m1, int2) every fake-quant value of a block is e2m1_code * 2^e_in where the outlier
+ * mask is clear and e2m1_code * 2^(e_out - e_in) where it is set (utils/quant.py:258), so one dense nibble per weight,
+ * one select bit per weight and the two E8M0 bytes per block of MSQ-T1 describe it exactly:
+ *   inlier plane : as MSQ-T1 (2 slots per tile, dword nf of a lane = the 8 e2m1 nibbles of fragment nf) -- the nibble of
+ *                  EVERY weight, inlier or outlier
+ *   out plane    : per tile 2 slots (kf) of 64 lanes x 4 B: the select bit of element j of fragment nf sits at bit
+ *                  16 (j & 1) + 4 nf + (j >> 1) of the lane's dword, so that shifting right by 4 nf + (j >> 1) and masking
+ *                  with 0x00010001 leaves the bits of the element pair (2 d, 2 d + 1) at the bottom of the two bf16 halves
+ *   scale plane  : 16 B per lane group with the MSQ-T1 byte meaning (byte nf*4 + kf*2 + {0: e_in + 127, 1: e_out - e_in + 127});
+ *                  block 32: 16 groups per tile (column c = l & 15), block 16: 32 groups, group (g >> 1) * 16 + c (lanes
+ *                  g and g ^ 1 share a block) -- exactly two scale bytes per block
+ * = tiles * (2048 + 512) + 2 N K / block bytes: 6.0 bits per weight at block 16, 5.5 at block 32.
+ * Canonical form: a zero is stored as code +0 with its select bit CLEAR whatever the mask said, so "bit set => code
+ * non-zero".  The decode converts every nibble with the inlier scale and adds (outlier byte - inlier byte) << 7 -- the
+ * factor 2^(e_out - 2 e_in) between the two readings, as a step of the bf16 exponent field -- to the halves whose bit
+ * is set; the pack kernel runs the same instruction sequence on every code and raises MSQ_STATUS_INEXACT if a value
+ * does not come back (intermediate or result outside the normal bf16 range, scale byte outside 1..254).  The packer
+ * builds it for variant 0 with round-to-nearest in one fused pass; other configurations return MSQ_ERR_UNSUPPORTED.
  * ------------------------------------------------------------------------- */
 int msq_packed_kinds(int inlier_fmt, int outlier_fmt, int* in_kind, int* out_kind);
-/* layout-aware form; MSQ_ERR_UNSUPPORTED when the formats cannot use the unified layout */
+/* layout-aware form; MSQ_ERR_UNSUPPORTED when the formats cannot use the unified / compact layout */
 int msq_packed_kinds_layout(int inlier_fmt, int outlier_fmt, int layout, int* in_kind, int* out_kind);
 int msq_packed_sizes(int64_t N, int64_t K, int block, int in_kind, int out_kind, int64_t* inl_bytes,
                      int64_t* out_bytes, int64_t* scale_bytes, int64_t* workspace_bytes);

@@ -7,7 +7,7 @@ buffer of the model, and a JSON header in the metadata describing each packed la
 rebuilt without re-quantising (and, for the 70B row-parallel configuration, shard by shard: every rank saves
 and loads its own file, `shard` / `world_size` are recorded).
 
-    header = {"format": "msq-packed", "version": 2, "shard": r, "world_size": G,
+    header = {"format": "msq-packed", "version": 2 (3 with a compact layer), "shard": r, "world_size": G,
               "layers": {"<module name>": {"in_features", "out_features", "block_size", "layout",
                                             "in_kind", "out_kind", "inlier_elem_format",
                                             "outlier_elem_format", "bias", "out_dtype"}}}
@@ -20,6 +20,11 @@ misleading "layer does not exist" / size mismatch.
 
 MX-operand layers (MXLinearW4A8: codes in the operand order of the scaled MFMA) are listed with
 ``"layout": "mx-operand"`` and ``"w_fmt"`` ("e2m1" plain MX-FP4, "e4m3" exactly packed fake-quant values).
+
+Version 3: a file that holds a layer in the compact layout (``"layout": "compact"``, plane kinds (1, 7): MSQ-C1 of include/msq.h).
+Only such files are written as version 3 -- a model without a compact layer is written exactly as before (version 2) -- so that a
+build which does not know the layout refuses the file with its "unsupported version" message instead of deriving other kinds;
+read_header accepts version 3 only together with such a layer.
 """
 import json
 
@@ -30,6 +35,7 @@ from ._lib import MsqError
 from .qlinear import K_MULT, N_MULT, FusedProjections, MXLinearW4A8, ProjectionSlice, QuantLinear, _ceil_to
 
 FORMAT, VERSION = "msq-packed", 2
+VERSION_COMPACT = 3                                      # written (and read) only for a file that holds a compact layer
 
 
 def _packed_layers(model):
@@ -51,6 +57,10 @@ def _fused_groups(model):
     return groups
 
 
+def _has_compact(layers):
+    return any(d.get("layout") == "compact" for d in layers.values())
+
+
 def save_packed(model, path, shard=0, world_size=1):
     """Write every tensor of `model` (packed planes included) and the layer table to `path`."""
     from safetensors.torch import save_file
@@ -68,7 +78,8 @@ def save_packed(model, path, shard=0, world_size=1):
                             padded_out=_ceil_to(m.out_features, N_MULT), padded_in=_ceil_to(m.in_features, K_MULT))
     for name, (parent, sibs, splits) in fused.items():            # fused q / k / v or gate / up: one packed weight, several stand-ins
         layers[name]["fused"] = dict(parent=parent, names=sibs, splits=splits)
-    header = dict(format=FORMAT, version=VERSION, shard=int(shard), world_size=int(world_size), layers=layers)
+    version = VERSION_COMPACT if _has_compact(layers) else VERSION
+    header = dict(format=FORMAT, version=version, shard=int(shard), world_size=int(world_size), layers=layers)
     tensors = {k: v.detach().contiguous().cpu() for k, v in model.state_dict().items()}
     save_file(tensors, path, metadata={"msq": json.dumps(header)})
     return header
@@ -81,9 +92,12 @@ def read_header(path):
     if "msq" not in meta:
         raise MsqError("%s is not an msq-packed checkpoint (no header)" % path)
     header = json.loads(meta["msq"])
-    if header.get("format") != FORMAT or int(header.get("version", -1)) > VERSION:
-        raise MsqError("unsupported checkpoint format %r version %r (this build reads %s versions 1..%d)"
-                       % (header.get("format"), header.get("version"), FORMAT, VERSION))
+    version = int(header.get("version", -1))
+    # version 3 is defined by its compact layer: a "version 3" header without one comes from some other definition of that number
+    known = version <= VERSION or (version == VERSION_COMPACT and _has_compact(header.get("layers") or {}))
+    if header.get("format") != FORMAT or not known:
+        raise MsqError("unsupported checkpoint format %r version %r (this build reads %s versions 1..%d, and version %d files that hold a compact layer)"
+                       % (header.get("format"), header.get("version"), FORMAT, VERSION, VERSION_COMPACT))
     return header
 
 

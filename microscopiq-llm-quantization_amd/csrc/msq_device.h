@@ -393,4 +393,29 @@ MSQ_HD float std_welford(const float (&x)[N], int correction) {
     return (float)__builtin_sqrt(m2 / den);
 }
 
+// ---------------------------------------------------------------------------
+// MSQ-C1 (compact layout, include/msq.h) decode of one dword of a fragment: elements (2 d, 2 d + 1) of the 8 e2m1 nibbles
+// `nib` -> two bf16 halves.  Every nibble is converted with the INLIER scale; where the element's select bit is set the
+// factor 2^(e_out - 2 e_in) between the two readings of a code is applied as a step of the bf16 exponent field:
+// `step` = ((outlier byte - inlier byte) << 7) mod 2^16 (held in both halves of a dword) added to that half (16-bit
+// wrap-around makes a negative step work; a set bit never meets a zero: canonical form).  `sel` = the lane's select dword
+// of this half tile, `sh` = 4 nf + d.  The pack kernel proves every code with this very function (k_pack_tile), the GEMMs
+// decode with it.  4 vector instructions per dword: convert, shift, and, packed 16-bit multiply-add (bit x step + value).
+// ---------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
+MSQ_D uint32_t sel_step(uint32_t scale_pair) {            // low 16 bits: inlier byte | outlier byte << 8
+    return (((((scale_pair >> 8) & 0xFFu) - (scale_pair & 0xFFu)) << 7) & 0xFFFFu) * 0x00010001u;
+}
+MSQ_D uint32_t sel_dword(uint32_t nib, float s_in, int d, uint32_t sel, int sh, uint32_t step) {
+    typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
+    uint32_t r;
+    if (d == 0) r = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(nib, s_in, 0));
+    else if (d == 1) r = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(nib, s_in, 1));
+    else if (d == 2) r = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(nib, s_in, 2));
+    else r = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(nib, s_in, 3));
+    const uint32_t m = (sel >> sh) & 0x00010001u;
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2_t, m) * __builtin_bit_cast(u16x2_t, step) + __builtin_bit_cast(u16x2_t, r));   // v_pk_mad_u16
+}
+#endif
+
 }  // namespace msq

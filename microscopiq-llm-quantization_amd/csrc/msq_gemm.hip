@@ -109,9 +109,16 @@ MSQ_D void load_tile(TileRegs& t, const uint8_t* inl_plane, const uint8_t* out_p
         } else { t.ext[0] = 0; t.ext[1] = 0; }
     } else if (IN_KIND != MSQ_PLANE_NONE) {
 #pragma unroll
-        for (int kf = 0; kf < 2; ++kf)
-            t.inl[kf] = *reinterpret_cast<const u32x4_t*>(inl_plane + ((tile * 2 + kf) * 64 + lane) * 16);
-        t.scl = *reinterpret_cast<const u32x4_t*>(scl_plane + (tile * scl_groups + (lane & (scl_groups - 1))) * 16);
+        for (int kf = 0; kf < 2; ++kf)     // (compact layout: the nibble plane IS the weight stream, read once like the code slots below)
+            t.inl[kf] = (NT && OUT_KIND == MSQ_PLANE_SEL) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(inl_plane + ((tile * 2 + kf) * 64 + lane) * 16))
+                                                         : *reinterpret_cast<const u32x4_t*>(inl_plane + ((tile * 2 + kf) * 64 + lane) * 16);
+        t.scl = *reinterpret_cast<const u32x4_t*>(scl_plane + (tile * scl_groups + scl_group(lane, scl_groups)) * 16);
+        if (OUT_KIND == MSQ_PLANE_SEL) {   // select bits: 2 slots (kf) of 64 lanes x 4 B
+            t.ext[0] = NT ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(out_plane + ((tile * 2 + 0) * 64 + lane) * 4))
+                          : *reinterpret_cast<const uint32_t*>(out_plane + ((tile * 2 + 0) * 64 + lane) * 4);
+            t.ext[1] = NT ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(out_plane + ((tile * 2 + 1) * 64 + lane) * 4))
+                          : *reinterpret_cast<const uint32_t*>(out_plane + ((tile * 2 + 1) * 64 + lane) * 4);
+        }
     }
 #pragma unroll
     for (int s = 0; s < OS; ++s)
@@ -227,12 +234,12 @@ k_qgemm3(const uint16_t* __restrict__ X, const uint8_t* __restrict__ inl_plane, 
     const int64_t ntiles = (int64_t)(N / TILE_N) * KT;
     PlaneRsrc pr;
     pr.inl = make_rsrc(inl_plane, ntiles * 2 * (OUT_KIND == MSQ_PLANE_U8X ? 256 : 1024));
-    pr.out = make_rsrc(out_plane, ntiles * 2 * HalfSlots<OUT_KIND>::n * 1024);
+    pr.out = make_rsrc(out_plane, OUT_KIND == MSQ_PLANE_SEL ? ntiles * 2 * 256 : ntiles * 2 * HalfSlots<OUT_KIND>::n * 1024);
     constexpr bool HAS_SCALE = HasScale<IN_KIND, OUT_KIND>::v;
     constexpr int SCLB = SclBytes<OUT_KIND>::n;               // scale bytes per lane group and tile
     pr.scl = make_rsrc(scl_plane, ntiles * scl_groups * SCLB);
     const int lane16 = lane * 16;
-    const int scl_lane_off = (lane & (scl_groups - 1)) * SCLB;
+    const int scl_lane_off = scl_group(lane, scl_groups) * SCLB;
     const uint32_t scl_tile_bytes = (uint32_t)scl_groups * (uint32_t)SCLB;
     auto load_scales = [&](uint32_t tile) -> u32x4_t {
         if (SCLB == 16) return __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(pr.scl, scl_lane_off, uni(tile * scl_tile_bytes), 0));
@@ -975,6 +982,8 @@ k_qgemv(const uint16_t* __restrict__ X, const uint8_t* __restrict__ inl_plane, c
 //    round trip per tile otherwise).
 // Per tile a wave loads four code slots (16 B per lane), the scale pair and, for U1X, two extension dwords; two tiles in flight
 // (DEEP3: three -- slower with cold weights: more bytes in flight than the DRAM pages like, see the launcher).
+// OUT_KIND = MSQ_PLANE_SEL (compact layout MSQ-C1; `ext_plane` = the nibble plane, `code_plane` = the select bits): per tile a wave loads
+// two nibble slots (16 B per lane), two select dwords and the 16 scale bytes of its lane group: 2560 + 256 / 512 B per tile instead of 4224.
 // Half strips over all of K for the 4096-wide projections (128 blocks) were built and measured slower than the split-K planes
 // of k_qgemv (down projection 14.7 -> 17.3 us): a CU keeps only so many bytes in flight, 128 CUs cannot pull what 256 can.
 // ---------------------------------------------------------------------------
@@ -982,8 +991,9 @@ template <int OUT_KIND, int MG, int WAVES, bool XPF, bool DEEP3 = false>
 __global__ void __launch_bounds__(64 * WAVES)
 k_qgemv_u(const uint16_t* __restrict__ X, const uint8_t* __restrict__ ext_plane, const uint8_t* __restrict__ code_plane,
           const uint8_t* __restrict__ scl_plane, int M, int N, int K, int kc, const float* __restrict__ bias, void* __restrict__ Y,
-          int y_kind, int x_f16) {
+          int y_kind, int x_f16, int scl_groups) {
     constexpr bool EXT = (OUT_KIND == MSQ_PLANE_U8X);
+    constexpr bool SEL = (OUT_KIND == MSQ_PLANE_SEL);
     constexpr int NFB = 4;                                       // 16-column fragments per block
     constexpr int R = MG * NFB * 4;                              // results per lane
     extern __shared__ __attribute__((aligned(16))) char smem_u[];
@@ -1009,10 +1019,20 @@ k_qgemv_u(const uint16_t* __restrict__ X, const uint8_t* __restrict__ ext_plane,
 #pragma unroll
     for (int j = 0; j < MG; ++j) { int m = j * 16 + c; m = m < M ? m : M - 1; xrow[j] = X + (int64_t)m * K + g * 8; }
 
-    struct UT { u32x4_t code[2][2]; uint32_t scl[2]; uint32_t ext[2]; };
+    struct UT { u32x4_t code[2][SEL ? 1 : 2]; uint32_t scl[SEL ? 4 : 2]; uint32_t ext[2]; };   // SEL: nibble slot, scale dword nf, select dwords
     struct XF { u32x4_t v[2][MG]; };
     auto load_u = [&](UT& t, int kt) {
         const int64_t tile = tile_row + kt;
+        if constexpr (SEL) {
+#pragma unroll
+            for (int kf = 0; kf < 2; ++kf) {
+                t.code[kf][0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(ext_plane + ((tile * 2 + kf) * 64 + lane) * 16));
+                t.ext[kf] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(code_plane + ((tile * 2 + kf) * 64 + lane) * 4));
+            }
+            const u32x4_t sc = *reinterpret_cast<const u32x4_t*>(scl_plane + (tile * scl_groups + scl_group(lane, scl_groups)) * 16);
+            t.scl[0] = sc[0]; t.scl[1] = sc[1]; t.scl[2] = sc[2]; t.scl[3] = sc[3];
+            return;
+        }
 #pragma unroll
         for (int kf = 0; kf < 2; ++kf)
 #pragma unroll
@@ -1058,9 +1078,13 @@ k_qgemv_u(const uint16_t* __restrict__ X, const uint8_t* __restrict__ ext_plane,
             }
 #pragma unroll
             for (int nf = 0; nf < NFB; ++nf) {
-                const u32x4_t o = cur.code[kf][nf >> 1];
-                const bf16x8_t wf = __builtin_bit_cast(bf16x8_t, dequant_frag_unified<OUT_KIND>(o[(nf & 1) * 2], o[(nf & 1) * 2 + 1],
-                                                                                               scale_operand(cur.scl[kf], nf), cur.ext[kf], nf));
+                bf16x8_t wf;
+                if constexpr (SEL) wf = __builtin_bit_cast(bf16x8_t, dequant_frag_sel(cur.code[kf][0][nf], cur.ext[kf], cur.scl[nf] >> (16 * kf), nf));
+                else {
+                    const u32x4_t o = cur.code[kf][nf >> 1];
+                    wf = __builtin_bit_cast(bf16x8_t, dequant_frag_unified<OUT_KIND>(o[(nf & 1) * 2], o[(nf & 1) * 2 + 1],
+                                                                                   scale_operand(cur.scl[kf], nf), cur.ext[kf], nf));
+                }
 #pragma unroll
                 for (int j = 0; j < MG; ++j)
                     acc[nf][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf[j], acc[nf][j], 0, 0, 0);
@@ -1233,10 +1257,19 @@ static int sig_bits(const msq_host::FmtInfo& f, int fmt_id) {
 
 int msq_packed_kinds_layout(int inlier_fmt, int outlier_fmt, int layout, int* in_kind, int* out_kind) {
     if (layout == MSQ_LAYOUT_PLANES) return msq_packed_kinds(inlier_fmt, outlier_fmt, in_kind, out_kind);
-    if (layout != MSQ_LAYOUT_UNIFIED) return fail2(MSQ_ERR_BAD_ARG, "msq_packed_kinds_layout: bad layout");
+    if (layout != MSQ_LAYOUT_UNIFIED && layout != MSQ_LAYOUT_COMPACT) return fail2(MSQ_ERR_BAD_ARG, "msq_packed_kinds_layout: bad layout");
     msq_host::FmtInfo fi, fo;
     if (!msq_host::format_info(inlier_fmt, &fi) || !msq_host::format_info(outlier_fmt, &fo))
         return fail2(MSQ_ERR_BAD_ARG, "msq_packed_kinds_layout: unknown element format");
+    if (layout == MSQ_LAYOUT_COMPACT) {                        // one e2m1 nibble per weight: both formats must lie on the e2m1 grid
+        const bool in_ok = inlier_fmt == MSQ_FMT_FP4_E2M1 || inlier_fmt == MSQ_FMT_INT2;
+        const bool out_ok = outlier_fmt == MSQ_FMT_FP4_E2M1 || outlier_fmt == MSQ_FMT_INT2;
+        if (!in_ok || !out_ok)
+            return fail2(MSQ_ERR_UNSUPPORTED, "msq_packed_kinds_layout: the compact layout holds fp4_e2m1 / int2 inliers with fp4_e2m1 / int2 outliers only (other outlier formats keep the unified or the two-plane layout)");
+        if (in_kind) *in_kind = MSQ_PLANE_FP4;
+        if (out_kind) *out_kind = MSQ_PLANE_SEL;
+        return MSQ_OK;
+    }
     const int si = sig_bits(fi, inlier_fmt), so = sig_bits(fo, outlier_fmt);
     const int sg = si > so ? si : so;
     if (fi.kind != 0 || sg > 5)
@@ -1254,6 +1287,15 @@ int msq_packed_sizes(int64_t N, int64_t K, int block, int in_kind, int out_kind,
         return fail2(MSQ_ERR_UNSUPPORTED, "msq_packed_sizes: block must be 8/16/32/64/128 and divide K");
     const int64_t tiles = (N / TILE_N) * (K / TILE_K);
     const int groups = block < 32 ? 64 : 16;
+    if (out_kind == MSQ_PLANE_SEL) {                           // compact layout: nibble plane + select bits + exactly two scale bytes per block
+        if (in_kind != MSQ_PLANE_FP4) return fail2(MSQ_ERR_BAD_ARG, "msq_packed_sizes: the select-bit plane goes with an e2m1 inlier plane");
+        if (block != 16 && block != 32) return fail2(MSQ_ERR_UNSUPPORTED, "msq_packed_sizes: the compact layout is built for block 16 and 32");
+        if (inl_bytes) *inl_bytes = tiles * 2 * 1024;
+        if (out_bytes) *out_bytes = tiles * 2 * 256;
+        if (scale_bytes) *scale_bytes = tiles * (block == 16 ? 32 : 16) * 16;
+        if (workspace_bytes) *workspace_bytes = 0;
+        return MSQ_OK;
+    }
     if (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X) {
         if (in_kind != MSQ_PLANE_NONE) return fail2(MSQ_ERR_BAD_ARG, "msq_packed_sizes: unified planes have no inlier plane");
         if (inl_bytes) *inl_bytes = (out_kind == MSQ_PLANE_U8X) ? tiles * 2 * 256 : 0;      // extension bits
@@ -1300,6 +1342,13 @@ int msq_outlier_pack(const float* W, void* inl_plane, void* out_plane, void* sca
         rc = msq_pack_fused_(W, inl_plane, out_plane, scale_plane, status_flag, N, K, block, inlier_fmt, outlier_fmt,
                              inlier_scale_bits, outlier_scale_bits, std_dev, rmode, flush_fp32_subnorms, ik, ok, stream);
         if (rc == MSQ_ERR_UNSUPPORTED) return fail2(rc, "msq_outlier_pack: the unified layout needs nearest rounding and block <= 64");
+        return rc;
+    }
+    if (layout == MSQ_LAYOUT_COMPACT) {
+        if (variant != MSQ_VARIANT_QUANT) return fail2(MSQ_ERR_UNSUPPORTED, "msq_outlier_pack: the compact layout packs the canonical quantiser (variant 0) only");
+        rc = msq_pack_fused_(W, inl_plane, out_plane, scale_plane, status_flag, N, K, block, inlier_fmt, outlier_fmt,
+                             inlier_scale_bits, outlier_scale_bits, std_dev, rmode, flush_fp32_subnorms, ik, ok, stream);
+        if (rc == MSQ_ERR_UNSUPPORTED) return fail2(rc, "msq_outlier_pack: the compact layout needs nearest rounding and scale bits 1..8");
         return rc;
     }
     // single-pass kernel for the common configurations (float/int inliers, nearest rounding, block <= 64) ...
@@ -1368,7 +1417,7 @@ int msq_outlier_unpack(const void* inl_plane, const void* out_plane, const void*
     const int64_t tiles = (N / TILE_N) * (K / TILE_K);
     const dim3 grid((unsigned)((tiles + 3) / 4)), blk(256);
     hipStream_t st = (hipStream_t)stream;
-    const int groups = block < 32 ? 64 : 16;
+    const int groups = (out_kind == MSQ_PLANE_SEL) ? (block < 32 ? 32 : 16) : (block < 32 ? 64 : 16);
 #define MSQ_UP(IK, OK)                                                                                               \
     do { if (out_dtype == 0) hipLaunchKernelGGL((k_unpack<IK, OK, float>), grid, blk, 0, st, (const uint8_t*)inl_plane,  \
                     (const uint8_t*)out_plane, (const uint8_t*)scale_plane, (float*)W_out, N, K, groups);              \
@@ -1380,6 +1429,7 @@ int msq_outlier_unpack(const void* inl_plane, const void* out_plane, const void*
     else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_BF16) MSQ_UP(MSQ_PLANE_FP4, MSQ_PLANE_BF16);
     else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8) MSQ_UP(MSQ_PLANE_NONE, MSQ_PLANE_U8);
     else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8X) MSQ_UP(MSQ_PLANE_NONE, MSQ_PLANE_U8X);
+    else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_SEL) MSQ_UP(MSQ_PLANE_FP4, MSQ_PLANE_SEL);
     else return fail2(MSQ_ERR_UNSUPPORTED, "msq_outlier_unpack: unsupported plane kinds");
 #undef MSQ_UP
     return check_launch2("msq_outlier_unpack");
@@ -1655,7 +1705,8 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
     }
     hipStream_t st0 = (hipStream_t)stream;
     const int y16 = (y_dtype == 1) ? 1 : 0;                       // fp16 output: the 16-bit kernels with the half conversion
-    const int groups0 = unified ? 16 : (block < 32 ? 64 : 16);
+    const bool compact = (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_SEL);
+    const int groups0 = unified ? 16 : (compact ? (block < 32 ? 32 : 16) : (block < 32 ? 64 : 16));
     // fp16 activations are converted inside the decode kernels only: where the bf16 call takes k_qgemm_sk the caller casts (one kernel, one
     // summation order for both activation dtypes: tests/test_gpu_n2_gemm.py::test_decode_kernels_take_fp16_activations)
     if (x_f16 && sk_rule(M, N, K, unified, out_kind))
@@ -1672,7 +1723,7 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
         const int nks = kcd ? 1 : (int)(((K / BK + kc - 1) / kc + 3) / 4);    // partial planes: one per four k-chunks
         // unified layouts, M <= 32, more than 128 strips: the single-launch kernel (MSQ_GEMV_U=0: the earlier kernels, tuning only)
         static const int gvu = [] { const char* e = getenv("MSQ_GEMV_U"); return e ? atoi(e) : 1; }();
-        if (gvu && N / TILE_N > 128 && in_kind == MSQ_PLANE_NONE && (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X)) {
+        if (gvu && N / TILE_N > 128 && ((in_kind == MSQ_PLANE_NONE && (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X)) || compact)) {
             const int64_t strips = N / TILE_N, KTv = K / TILE_K;
             // Waves per block (= k-runs per strip) so that the grid has ~1000-2000 waves, two tiles in flight each: a COLD read stream
             // is fastest with a few MB in flight (scripts/experiments/hbm_read.hip: 1024 waves x 4 KB reach 6 TB/s, 8192 x 8 KB only
@@ -1689,15 +1740,15 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
                  const size_t l_ = (size_t)WV * MGV * 16 * 64 * 4;                                                        \
                  if (attr_needed(once_)) { hipFuncSetAttribute((const void*)k_qgemv_u<OK, MGV, WV, XP, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l_); attr_done(once_); } \
                  hipLaunchKernelGGL((k_qgemv_u<OK, MGV, WV, XP, false>), ugrid, dim3(64 * WV), l_, st0, (const uint16_t*)X, (const uint8_t*)inl_plane, (const uint8_t*)out_plane, \
-                                    (const uint8_t*)scale_plane, (int)M, (int)N, (int)K, kcu, bias, Y, yk, x_f16); } while (0)
+                                    (const uint8_t*)scale_plane, (int)M, (int)N, (int)K, kcu, bias, Y, yk, x_f16, groups0); } while (0)
             // activation prefetch: from two rows on (one row: every lane reads the same line, an L1 hit), where the registers allow
 #define MSQ_GVUW(OK, WV) do { if (mg == 1) { if (M > 1) MSQ_GVU1(OK, 1, WV, true); else MSQ_GVU1(OK, 1, WV, false); } else if (mg == 2) MSQ_GVU1(OK, 2, WV, false); else MSQ_GVU1(OK, 4, WV, false); } while (0)
 #define MSQ_GVU(OK) do { if (wv == 2) MSQ_GVUW(OK, 2); else if (wv == 4) MSQ_GVUW(OK, 4); else if (wv == 8) MSQ_GVUW(OK, 8); else MSQ_GVUW(OK, 16); } while (0)
-            if (out_kind == MSQ_PLANE_U8) MSQ_GVU(MSQ_PLANE_U8); else MSQ_GVU(MSQ_PLANE_U8X);
+            if (out_kind == MSQ_PLANE_U8) MSQ_GVU(MSQ_PLANE_U8); else if (compact) MSQ_GVU(MSQ_PLANE_SEL); else MSQ_GVU(MSQ_PLANE_U8X);
 #undef MSQ_GVU
 #undef MSQ_GVUW
 #undef MSQ_GVU1
-            return check_launch2("msq_qlinear_bf16(decode, unified layouts)");
+            return check_launch2("msq_qlinear_bf16(decode, single launch over all of K)");
         }
         if (kcd || (workspace && workspace_bytes >= (int64_t)nks * M * N * 4)) {
             const dim3 vgrid((unsigned)((N / TILE_N) * nks));
@@ -1719,6 +1770,7 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
             else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_BF16) MSQ_GV(MSQ_PLANE_FP4, MSQ_PLANE_BF16);
             else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8) MSQ_GV(MSQ_PLANE_NONE, MSQ_PLANE_U8);
             else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8X) MSQ_GV(MSQ_PLANE_NONE, MSQ_PLANE_U8X);
+            else if (compact) MSQ_GV(MSQ_PLANE_FP4, MSQ_PLANE_SEL);
             else return fail2(MSQ_ERR_UNSUPPORTED, "msq_qlinear_bf16: unsupported plane kinds");
 #undef MSQ_GV
 #undef MSQ_GV1
@@ -1782,6 +1834,7 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
          else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_BF16) MSQ_LAUNCH(KERN, MSQ_PLANE_FP4, MSQ_PLANE_BF16); \
          else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8) MSQ_LAUNCH(KERN, MSQ_PLANE_NONE, MSQ_PLANE_U8); \
          else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8X) MSQ_LAUNCH(KERN, MSQ_PLANE_NONE, MSQ_PLANE_U8X); \
+         else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_SEL) MSQ_LAUNCH(KERN, MSQ_PLANE_FP4, MSQ_PLANE_SEL); \
          else return fail2(MSQ_ERR_UNSUPPORTED, "msq_qlinear_bf16: unsupported plane kinds"); } while (0)
     // Eight waves along n (one block of 128 x 512 per CU instead of two of 128 x 256): the eight waves share ONE activation
     // tile, so every wave issues half the LDS-DMA pieces and the CU pulls half the activation bytes from L2 per K-step.
@@ -2231,6 +2284,13 @@ int msq_qlinear_kernel_name(int64_t M, int64_t N, int64_t K, int out_kind, int m
         snprintf(buf, cap, "k_qgemm_sk<%d, %s, %d, %d, %d, %d>", out_kind, yt, (f == 1 || f == 5) ? 4 : 8, (f == 3 || f == 5 || f == 6) ? 2 : 1,
                  (f == 1 || f == 4) ? 8 : ((f == 2 || f == 5 || f == 6) ? 4 : 2), f == 4 ? 1 : ((f == 3 || f == 5) ? 3 : 2));
     }
+    else if (out_kind == MSQ_PLANE_SEL && fam == MSQ_KERNEL_DECODE) {      // compact layout: the instantiation itself
+        const int mg = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
+        const int64_t strips = N / TILE_N;
+        if (strips > 128) snprintf(buf, cap, "k_qgemv_u<7, %d, %d>", mg, strips <= 256 ? 8 : (strips <= 640 ? 4 : 2));
+        else snprintf(buf, cap, "k_qgemv<1, 7, %d, 4>", mg);
+    }
+    else if (out_kind == MSQ_PLANE_SEL && fam == MSQ_KERNEL_GEMM128) snprintf(buf, cap, "k_qgemm3<1, 7, %s>", yt);
     else if (fam == MSQ_KERNEL_DECODE) snprintf(buf, cap, "k_qgemv_u / k_qgemv<out kind %d>", out_kind);
     else if (fam == MSQ_KERNEL_GEMM128) snprintf(buf, cap, "k_qgemm3<out kind %d, %s>", out_kind, yt);
     else if (fam == MSQ_KERNEL_PERSISTENT) snprintf(buf, cap, "k_qgemm256p<%d, %s>", out_kind, yt);

@@ -112,12 +112,25 @@ MSQ_D u32x4_t dequant_frag_unified(uint32_t o0, uint32_t o1, float s, uint32_t e
     return r;
 }
 
+// compact layout (MSQ-C1): e2m1 nibble of every weight + select bit; the two scale bytes of the block as (inlier, outlier) pair
+MSQ_D u32x4_t dequant_frag_sel(uint32_t nib, uint32_t sel, uint32_t scale_pair, int nf) {
+    const float s_in = __builtin_bit_cast(float, (scale_pair & 0xFFu) << 23);
+    const uint32_t step = sel_step(scale_pair);
+    u32x4_t r;
+    r[0] = sel_dword(nib, s_in, 0, sel, nf * 4 + 0, step); r[1] = sel_dword(nib, s_in, 1, sel, nf * 4 + 1, step);
+    r[2] = sel_dword(nib, s_in, 2, sel, nf * 4 + 2, step); r[3] = sel_dword(nib, s_in, 3, sel, nf * 4 + 3, step);
+    return r;
+}
+// lane -> group of the scale plane: `groups` = 16 (one per column), 64 (one per lane) or 32 (compact layout, block 16: lanes
+// g and g ^ 1 share a block: group (g >> 1) * 16 + c)
+MSQ_D int scl_group(int lane, int groups) { return groups == 32 ? ((lane & 15) | ((lane >> 1) & 16)) : (lane & (groups - 1)); }
+
 // all 8 fragments of one 64x64 tile for this lane
 struct TileRegs {
     u32x4_t inl[2];      // [kf]  dword nf
     u32x4_t out[8];      // 8-bit kinds use [0..3] = (kf*2 + nf/2); bf16 kind uses [kf*4 + nf]
     u32x4_t scl;         // dword nf: bytes kf*2 + io   (unified: dword kf: byte nf)
-    uint32_t ext[2];     // unified U8X: extension bits of half kf
+    uint32_t ext[2];     // unified U8X: extension bits of half kf; compact (SEL): select bits of half kf
 };
 
 template <int IN_KIND, int OUT_KIND>
@@ -128,6 +141,7 @@ MSQ_D u32x4_t tile_frag(const TileRegs& t, int nf, int kf) {
     }
     if (IN_KIND == MSQ_PLANE_NONE) return t.out[kf * 4 + nf];
     const uint32_t sd = t.scl[nf];
+    if (OUT_KIND == MSQ_PLANE_SEL) return dequant_frag_sel(t.inl[kf][nf], t.ext[kf], sd >> (16 * kf), nf);
     const float s_in = scale_operand(sd, kf * 2);
     if (OUT_KIND == MSQ_PLANE_BF16) {
         u32x4_t r = dequant_frag_in_only(t.inl[kf][nf], s_in);
@@ -147,7 +161,7 @@ MSQ_D u32x4_t tile_frag(const TileRegs& t, int nf, int kf) {
 MSQ_D int frag_n(int lane, int f) { return f * 16 + (lane & 15); }
 MSQ_D int frag_k(int lane, int kf) { return kf * 32 + (lane >> 4) * 8; }
 
-template <int OUT_KIND> struct OutSlots { static constexpr int n = (OUT_KIND == MSQ_PLANE_BF16) ? 8 : 4; };
+template <int OUT_KIND> struct OutSlots { static constexpr int n = (OUT_KIND == MSQ_PLANE_BF16) ? 8 : ((OUT_KIND == MSQ_PLANE_SEL) ? 0 : 4); };   // SEL: 2 x 256 B of select bits instead
 // bytes of the scale plane per tile and lane group
 template <int OUT_KIND> struct SclBytes { static constexpr int n = IsUnified<OUT_KIND>::v ? 8 : 16; };
 
@@ -161,17 +175,17 @@ template <int OUT_KIND> struct SclBytes { static constexpr int n = IsUnified<OUT
 // current one (sched_group_barrier pins the interleave), and only one half-step of packed data
 // is in flight per buffer (register budget: 128 acc + 32 wf + <=48 packed + 12 xf).
 // ---------------------------------------------------------------------------
-template <int OUT_KIND> struct HalfSlots { static constexpr int n = (OUT_KIND == MSQ_PLANE_BF16) ? 4 : 2; };
+template <int OUT_KIND> struct HalfSlots { static constexpr int n = (OUT_KIND == MSQ_PLANE_BF16) ? 4 : ((OUT_KIND == MSQ_PLANE_SEL) ? 0 : 2); };
 // vector-memory loads one half-step issues for the packed operand (vmcnt bookkeeping)
 template <int IN_KIND, int OUT_KIND> struct HalfLoads {
-    static constexpr int n = (IN_KIND != MSQ_PLANE_NONE ? 1 : 0) + (((MSQ_ABL & 256) && IsUnified<OUT_KIND>::v) ? 1 : HalfSlots<OUT_KIND>::n) + (OUT_KIND == MSQ_PLANE_U8X ? 1 : 0);
+    static constexpr int n = (IN_KIND != MSQ_PLANE_NONE ? 1 : 0) + (((MSQ_ABL & 256) && IsUnified<OUT_KIND>::v) ? 1 : HalfSlots<OUT_KIND>::n) + ((OUT_KIND == MSQ_PLANE_U8X || OUT_KIND == MSQ_PLANE_SEL) ? 1 : 0);
 };
 
 template <int IN_KIND, int OUT_KIND>
 struct HalfRegs {
     u32x4_t inl;
-    u32x4_t out[HalfSlots<OUT_KIND>::n];
-    uint32_t ext;        // U8X: extension bits of this half
+    u32x4_t out[HalfSlots<OUT_KIND>::n ? HalfSlots<OUT_KIND>::n : 1];
+    uint32_t ext;        // U8X: extension bits of this half; SEL: its select bits
 };
 
 // --- packed-plane loads through buffer descriptors: the per-lane offset (lane * 16) never changes and the
@@ -213,6 +227,8 @@ MSQ_D void load_half_buf(HalfRegs<IN_KIND, OUT_KIND>& h, const PlaneRsrc& r, int
     }
     if (OUT_KIND == MSQ_PLANE_U8X)     // extension plane rides in the inlier descriptor: 64 lanes x 4 B per half
         h.ext = __builtin_amdgcn_raw_buffer_load_b32(r.inl, lane16 >> 2, uni(tile2kf * 256u), 0);
+    if (OUT_KIND == MSQ_PLANE_SEL)     // select bits ARE the out plane: 64 lanes x 4 B per half
+        h.ext = __builtin_amdgcn_raw_buffer_load_b32(r.out, lane16 >> 2, uni(tile2kf * 256u), 0);
 }
 
 // one quarter of a half-step's conversion work: fragment nf = q/2, dwords 2*(q%2) .. +1
@@ -233,6 +249,12 @@ MSQ_D void convert_quarter(u32x4_t (&wf)[4], const HalfRegs<IN_KIND, OUT_KIND>& 
         return;
     }
     const float s_in = scale_operand(scl[nf], kf * 2);
+    if (OUT_KIND == MSQ_PLANE_SEL) {   // convert with the inlier scale, step the exponent of the halves whose select bit is set
+        const uint32_t step = sel_step(scl[nf] >> (16 * kf));
+        wf[nf][2 * hh] = sel_dword(h.inl[nf], s_in, 2 * hh, h.ext, nf * 4 + 2 * hh, step);
+        wf[nf][2 * hh + 1] = sel_dword(h.inl[nf], s_in, 2 * hh + 1, h.ext, nf * 4 + 2 * hh + 1, step);
+        return;
+    }
     uint32_t r0, r1;
     if (hh == 0) {
         r0 = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(h.inl[nf], s_in, 0));
@@ -263,7 +285,7 @@ MSQ_D void keep_live1(uint32_t& v) { asm volatile("" : "+v"(v)); }
 template <int IN_KIND, int OUT_KIND>
 MSQ_D void keep_live(HalfRegs<IN_KIND, OUT_KIND>& h) {
     if (IN_KIND != MSQ_PLANE_NONE) keep_live4(h.inl);
-    if (OUT_KIND == MSQ_PLANE_U8X) keep_live1(h.ext);
+    if (OUT_KIND == MSQ_PLANE_U8X || OUT_KIND == MSQ_PLANE_SEL) keep_live1(h.ext);
 #pragma unroll
     for (int s = 0; s < HalfSlots<OUT_KIND>::n; ++s) keep_live4(h.out[s]);
 }

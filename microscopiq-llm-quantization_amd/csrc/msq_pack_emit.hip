@@ -21,6 +21,9 @@ extern "C" void msq_set_error_(const char* msg);
 //      (overlaying the fp32 tile);
 //   3. every lane gathers its MFMA fragments (layout 1: n = 16 nf + (l & 15), k = 32 kf + 8 (l >> 4) + j)
 //      and stores the slots: 64 lanes x 16 B = one coalesced 1 KiB store per slot.
+// OUT_KIND = MSQ_PLANE_SEL (compact layout MSQ-C1, BS 16 / 32): the nibble plane takes the e2m1 code of EVERY element -- cvt_fp4 of
+// the value over the inlier scale, or over the outlier scale where the mask is set -- and the out plane one select bit per element
+// (mask && code != 0: a zero is stored as +0 with its bit clear); each code is proven with sel_dword, the GEMMs' own decode.
 // ===========================================================================
 template <int BS, int IN_KIND, int OUT_KIND, int HW>
 __global__ void __launch_bounds__(256)
@@ -61,6 +64,9 @@ k_pack_tile(const float* __restrict__ W, uint8_t* __restrict__ inl_plane, uint8_
     uint32_t* inlT = reinterpret_cast<uint32_t*>(wl + INL_OFF);
     uint16_t* sclT = reinterpret_cast<uint16_t*>(wl + SCL_OFF);
     uint32_t* outT = reinterpret_cast<uint32_t*>(wl + OUT_OFF);
+    uint8_t* selT = reinterpret_cast<uint8_t*>(wl + OUT_OFF);   // SEL: one byte per (row, 8-k group): bits 0-3 = elements 0, 2, 4, 6, bits 4-7 = elements 1, 3, 5, 7
+    constexpr bool SEL = (OUT_KIND == MSQ_PLANE_SEL);
+    static_assert(!SEL || BS == 16 || BS == 32, "compact layout: block 16 or 32");
     int status = 0;
     // 2. quantise the blocks of this row; codes come from the hardware converts (v_cvt_scalef32_pk_fp4_f32 /
     //    _fp8_f32: the quantised values are already on the grid, so the conversion is exact) and are verified
@@ -86,6 +92,41 @@ k_pack_tile(const float* __restrict__ W, uint8_t* __restrict__ inl_plane, uint8_
             const int k8 = j * (BS / 8) + t8;                    // 8-k group index inside the tile (0..7)
             uint32_t iw = 0, ow[4] = {0, 0, 0, 0};
             bool ok = true;
+            if constexpr (SEL) {
+                const uint32_t step = sel_step(bi | (bo << 8));
+                uint32_t sb = 0;                                 // select bits of this 8-k group, in the order of selT
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const int e0 = t8 * 8 + 2 * p, e1 = e0 + 1;
+                    const bool m0 = (mkw[e0 >> 5] >> (e0 & 31)) & 1u, m1 = (mkw[e1 >> 5] >> (e1 & 31)) & 1u;
+                    const float q0 = (m0 ? (a[e0] * sc_in) * rc_out : a[e0] * rc_in) + 0.0f, q1 = (m1 ? (a[e1] * sc_in) * rc_out : a[e1] * rc_in) + 0.0f;
+                    if (p == 0) iw = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(iw, q0, q1, 1.0f, 0);
+                    else if (p == 1) iw = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(iw, q0, q1, 1.0f, 1);
+                    else if (p == 2) iw = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(iw, q0, q1, 1.0f, 2);
+                    else iw = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(iw, q0, q1, 1.0f, 3);
+                }
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const int e0 = t8 * 8 + 2 * p, e1 = e0 + 1;
+                    const bool m0 = (mkw[e0 >> 5] >> (e0 & 31)) & 1u, m1 = (mkw[e1 >> 5] >> (e1 & 31)) & 1u;
+                    if (m0 && ((iw >> (8 * p)) & 7u)) sb |= 1u << p;
+                    if (m1 && ((iw >> (8 * p + 4)) & 7u)) sb |= 16u << p;
+                }
+                // the dword the decode sees: element pair p at bits (p, 16 + p) once shifted by 4 nf -- verify with nf = 0
+                const uint32_t selw = (sb & 0xFu) | ((sb >> 4) << 16);
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const float v0 = a[t8 * 8 + 2 * p], v1 = a[t8 * 8 + 2 * p + 1];
+                    const uint32_t d = sel_dword(iw, s_in_op, p, selw, p, step);
+                    const uint32_t expect = (f2u(v0) >> 16) | (f2u(v1) & 0xFFFF0000u);
+                    ok = ok && (d == expect) && (((f2u(v0) | f2u(v1)) & 0xFFFFu) == 0u);
+                }
+                if (!ok && !(status & MSQ_STATUS_NAN)) status |= MSQ_STATUS_INEXACT;
+                inlT[lane * INL_STRIDE + k8] = iw;
+                sclT[lane * 8 + k8] = (uint16_t)(bi | (bo << 8));
+                selT[lane * 8 + k8] = (uint8_t)sb;
+                continue;
+            }
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const int e0 = t8 * 8 + 2 * p, e1 = e0 + 1;
@@ -155,6 +196,21 @@ k_pack_tile(const float* __restrict__ W, uint8_t* __restrict__ inl_plane, uint8_
 #pragma unroll
     for (int kf = 0; kf < 2; ++kf) {
         uint32_t inl4[4];
+        if constexpr (SEL) {
+            uint32_t sw = 0;
+#pragma unroll
+            for (int nf = 0; nf < 4; ++nf) {
+                const int n = nf * 16 + c, k8 = kf * 4 + g;
+                inl4[nf] = inlT[n * INL_STRIDE + k8];
+                const uint32_t s = sclT[n * 8 + k8];
+                sc[nf] |= s << (16 * kf);
+                const uint32_t b = selT[n * 8 + k8];
+                sw |= ((b & 0xFu) << (4 * nf)) | ((b >> 4) << (16 + 4 * nf));
+            }
+            *reinterpret_cast<uint4*>(inl_plane + ((tile * 2 + kf) * 64 + lane) * 16) = make_uint4(inl4[0], inl4[1], inl4[2], inl4[3]);
+            *reinterpret_cast<uint32_t*>(out_plane + ((tile * 2 + kf) * 64 + lane) * 4) = sw;
+            continue;
+        }
 #pragma unroll
         for (int nf = 0; nf < 4; ++nf) {
             const int n = nf * 16 + c, k8 = kf * 4 + g;
@@ -172,7 +228,10 @@ k_pack_tile(const float* __restrict__ W, uint8_t* __restrict__ inl_plane, uint8_
         if (IN_KIND != MSQ_PLANE_NONE)
             *reinterpret_cast<uint4*>(inl_plane + ((tile * 2 + kf) * 64 + lane) * 16) = make_uint4(inl4[0], inl4[1], inl4[2], inl4[3]);
     }
-    if (IN_KIND != MSQ_PLANE_NONE) {
+    if constexpr (SEL) {                                           // exactly two bytes per block: 32 groups (g >> 1, c) at block 16, 16 groups (c) at block 32
+        if (BS == 16 ? ((g & 1) == 0) : (g == 0))
+            *reinterpret_cast<uint4*>(scl_plane + (tile * (BS == 16 ? 32 : 16) + (BS == 16 ? (g >> 1) * 16 + c : c)) * 16) = make_uint4(sc[0], sc[1], sc[2], sc[3]);
+    } else if (IN_KIND != MSQ_PLANE_NONE) {
         const bool per_lane = BS < 32;
         const int groups = per_lane ? 64 : 16;
         if (per_lane || g == 0)
@@ -192,6 +251,7 @@ extern "C" int msq_pack_fused_(const float* W, void* inl_plane, void* out_plane,
     msq_host::FmtInfo fi, fo;
     if (!msq_host::format_info(inlier_fmt, &fi) || !msq_host::format_info(outlier_fmt, &fo)) return MSQ_ERR_UNSUPPORTED;
     if (fi.kind != 0 || rmode != 0 || !(block == 8 || block == 16 || block == 32 || block == 64)) return MSQ_ERR_UNSUPPORTED;
+    if (out_kind == MSQ_PLANE_SEL && (in_kind != MSQ_PLANE_FP4 || (block != 16 && block != 32))) return MSQ_ERR_UNSUPPORTED;
     if (in_sb <= 0 || out_sb <= 0 || in_sb > 8 || out_sb > 8) return MSQ_ERR_UNSUPPORTED;
     OutlierArgs A;
     A.fi = Fmt{fi.kind, fi.ebits, fi.mbits, fi.emax, fi.max_norm};
@@ -214,6 +274,10 @@ extern "C" int msq_pack_fused_(const float* W, void* inl_plane, void* out_plane,
     else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_FP8) { if (hw == 1) MSQ_PTB(MSQ_PLANE_FP4, MSQ_PLANE_FP8, 1); else MSQ_PTB(MSQ_PLANE_FP4, MSQ_PLANE_FP8, 0); }
     else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_BF8) { if (hw == 1) MSQ_PTB(MSQ_PLANE_FP4, MSQ_PLANE_BF8, 1); else MSQ_PTB(MSQ_PLANE_FP4, MSQ_PLANE_BF8, 0); }
     else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_BF16) { if (hw == 2) MSQ_PTB(MSQ_PLANE_FP4, MSQ_PLANE_BF16, 2); else MSQ_PTB(MSQ_PLANE_FP4, MSQ_PLANE_BF16, 0); }
+    else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_SEL) {
+        if (block == 16) { if (hw == 1) MSQ_PT(16, MSQ_PLANE_FP4, MSQ_PLANE_SEL, 1); else MSQ_PT(16, MSQ_PLANE_FP4, MSQ_PLANE_SEL, 0); }
+        else { if (hw == 1) MSQ_PT(32, MSQ_PLANE_FP4, MSQ_PLANE_SEL, 1); else MSQ_PT(32, MSQ_PLANE_FP4, MSQ_PLANE_SEL, 0); }
+    }
     else if (in_kind == MSQ_PLANE_NONE && (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X))
         return msq_pack_unified_(W, inl_plane, out_plane, scale_plane, &A, N, K, block, out_kind, hw, stream);
     else return MSQ_ERR_UNSUPPORTED;

@@ -63,14 +63,15 @@ class PackedWeight:
         return 8.0 * self.nbytes / (self.n * self.k)
 
 
-LAYOUT_PLANES, LAYOUT_UNIFIED = 0, 1
-_LAYOUTS = {"planes": LAYOUT_PLANES, "unified": LAYOUT_UNIFIED, LAYOUT_PLANES: LAYOUT_PLANES,
-            LAYOUT_UNIFIED: LAYOUT_UNIFIED}
+LAYOUT_PLANES, LAYOUT_UNIFIED, LAYOUT_COMPACT = 0, 1, 2
+_LAYOUTS = {"planes": LAYOUT_PLANES, "unified": LAYOUT_UNIFIED, "compact": LAYOUT_COMPACT, LAYOUT_PLANES: LAYOUT_PLANES,
+            LAYOUT_UNIFIED: LAYOUT_UNIFIED, LAYOUT_COMPACT: LAYOUT_COMPACT}
 
 
 def packed_kinds(inlier_elem_format, outlier_elem_format, layout="planes"):
     """Plane kinds of a packed layout: "planes" = MSQ-T1 (inlier plane + outlier plane, two scales per
-    block), "unified" = MSQ-U1 (one e4m3 code per weight [+ extension bit], one scale per 32 k)."""
+    block), "unified" = MSQ-U1 (one e4m3 code per weight [+ extension bit], one scale per 32 k), "compact" = MSQ-C1
+    (one e2m1 nibble + one select bit per weight, two scales per block: int2 / fp4 inliers with int2 / fp4 outliers)."""
     ik, ok = C.c_int(), C.c_int()
     check(lib().msq_packed_kinds_layout(format_id(inlier_elem_format), format_id(outlier_elem_format),
                                         _LAYOUTS[layout], C.byref(ik), C.byref(ok)), "msq_packed_kinds_layout")
@@ -91,8 +92,9 @@ def pack_weight(W, inlier_scale_bits=8, outlier_scale_bits=8, inlier_elem_format
     to the kernels' tile grid (``PackedWeight.N / K``), the logical shape is kept in ``PackedWeight.n / k``.
 
     layout: "planes" (MSQ-T1), "unified" (MSQ-U1, smaller and faster; raises MsqError if a 32-k group
-    cannot be represented exactly) or "auto" (unified when the formats allow it and every group is
-    exact, otherwise planes).
+    cannot be represented exactly), "auto" (unified when the formats allow it and every group is
+    exact, otherwise planes) or "compact" (MSQ-C1, opt-in: int2 / fp4 inliers with int2 / fp4 outliers at block 16 or 32
+    in 6.0 / 5.5 bits per weight; float32 compute only; raises MsqError for other formats / blocks or an inexact block).
 
     ``compute_dtype`` as quant.outlier_fakequant: an fp16 / bf16 weight is by default quantised IN its dtype (what the
     reference's RTN harness does with a half checkpoint, llm/llama.py:238), so that the packed layer holds exactly the
@@ -107,6 +109,9 @@ def pack_weight(W, inlier_scale_bits=8, outlier_scale_bits=8, inlier_elem_format
     if compute_dtype not in ("input", "float32"):
         raise MsqError("compute_dtype must be 'input' or 'float32'")
     n, k = W.shape
+    if layout == "compact" and compute_dtype == "input" and W.dtype in (torch.float16, torch.bfloat16):
+        raise MsqError("pack_weight(layout='compact'): a %s weight quantised in its own dtype is packed from its values (pack_values), which the "
+                       "compact layout does not take; pass compute_dtype='float32'" % str(W.dtype).replace("torch.", ""))
     if (compute_dtype == "input" and W.dtype in (torch.float16, torch.bfloat16) and variant == 0
             and not str(inlier_elem_format).startswith("posit") and not str(outlier_elem_format).startswith("posit")):
         from .quant import outlier_fakequant
@@ -154,8 +159,13 @@ def pack_weight(W, inlier_scale_bits=8, outlier_scale_bits=8, inlier_elem_format
 def _pack(Wf, inlier_scale_bits, outlier_scale_bits, inlier_elem_format, outlier_elem_format, std_dev, block_size,
           round, flush_fp32_subnorms, variant, layout, n=None, k=None):
     N, K = Wf.shape
-    ik, ok = packed_kinds(inlier_elem_format, outlier_elem_format, layout)
-    ib, ob, sb, wb = packed_sizes(N, K, block_size, ik, ok)
+    try:
+        ik, ok = packed_kinds(inlier_elem_format, outlier_elem_format, layout)
+        ib, ob, sb, wb = packed_sizes(N, K, block_size, ik, ok)
+    except MsqError as e:
+        if layout == "compact":
+            raise MsqError("pack_weight(layout='compact'): %s" % e)
+        raise
     dev = Wf.device
     inl = torch.empty(ib, dtype=torch.uint8, device=dev) if ib else None
     out = torch.empty(ob, dtype=torch.uint8, device=dev)
@@ -177,7 +187,12 @@ def _pack(Wf, inlier_scale_bits, outlier_scale_bits, inlier_elem_format, outlier
     return PackedWeight(inl, out, scl, N, K, block_size, ik, ok, n, k)
 
 
-PLANE_NONE, PLANE_BF16, PLANE_U8, PLANE_U8X = 0, 4, 5, 6
+PLANE_NONE, PLANE_BF16, PLANE_U8, PLANE_U8X, PLANE_SEL = 0, 4, 5, 6, 7
+
+
+def _layout_of(out_kind):
+    """layout name of a packed weight's outlier-plane kind"""
+    return {PLANE_U8: "unified", PLANE_U8X: "unified", PLANE_SEL: "compact"}.get(out_kind, "planes")
 
 
 def pack_values(Wq, kinds=(PLANE_U8, PLANE_U8X, PLANE_BF16)):
@@ -680,7 +695,7 @@ class QuantLinear(nn.Module):
         m.in_features, m.out_features, m.block_size = in_features, out_features, 32
         m.inlier_elem_format = m.outlier_elem_format = "values"
         m.out_dtype = out_dtype
-        m.layout = {PLANE_U8: "unified", PLANE_U8X: "unified", PLANE_BF16: "planes"}[out_kind]
+        m.layout = _layout_of(out_kind)
         m.in_kind, m.out_kind = PLANE_NONE, out_kind
         ib, ob, sb, _ = packed_sizes(_ceil_to(out_features, N_MULT), _ceil_to(in_features, K_MULT), 32, PLANE_NONE, out_kind)
         m.register_buffer("inl_plane", torch.zeros(ib, dtype=torch.uint8, device=device))
@@ -702,7 +717,7 @@ class QuantLinear(nn.Module):
         m.in_features, m.out_features, m.block_size = linear.in_features, linear.out_features, 32
         m.inlier_elem_format = m.outlier_elem_format = "values"
         m.out_dtype = out_dtype
-        m.layout = {PLANE_U8: "unified", PLANE_U8X: "unified", PLANE_BF16: "planes"}[P.out_kind]
+        m.layout = _layout_of(P.out_kind)
         m.in_kind, m.out_kind = P.in_kind, P.out_kind
         dev = linear.weight.device
         m.register_buffer("inl_plane", P.inl if P.inl is not None else torch.zeros(0, dtype=torch.uint8, device=dev))
@@ -723,7 +738,7 @@ class QuantLinear(nn.Module):
         # single-plane kinds are what pack_values / empty_single_plane produce: a checkpoint reloads them as such
         m.inlier_elem_format = m.outlier_elem_format = "values" if (P.in_kind == PLANE_NONE and P.block == 32) else "packed"
         m.out_dtype = out_dtype
-        m.layout = "unified" if P.out_kind in (PLANE_U8, PLANE_U8X) else "planes"
+        m.layout = _layout_of(P.out_kind)
         m.in_kind, m.out_kind = P.in_kind, P.out_kind
         dev = P.out.device
         m.register_buffer("inl_plane", P.inl if P.inl is not None else torch.zeros(0, dtype=torch.uint8, device=dev))
@@ -807,6 +822,11 @@ class ProjectionSlice(nn.Module):
         return self.shared().slice(self.index, x)
 
 
+def _compute_kw(layout):
+    """from_linear arguments that go with a layout: the compact layout is packed by the fused float32 quantise + pack launch only"""
+    return dict(compute_dtype="float32") if layout == "compact" else {}
+
+
 def fuse_projections(parent, names, quantizer=None, layout="auto", path="bf16"):
     """Replace the nn.Linear children ``names`` of ``parent`` (same in_features, same bias-ness) by ProjectionSlices of one
     packed module.  ``quantizer`` None = the weights already hold fake-quant values (pack_values / from_values)."""
@@ -825,7 +845,7 @@ def fuse_projections(parent, names, quantizer=None, layout="auto", path="bf16"):
         proj = MXLinearW4A8.from_values(W, cat.bias.data if cat.bias is not None else None, out_dtype=od) if quantizer is None \
             else MXLinearW4A8.from_linear(cat, out_dtype=od)
     else:
-        proj = QuantLinear.from_dense(cat) if quantizer is None else QuantLinear.from_linear(cat, quantizer, layout=layout)
+        proj = QuantLinear.from_dense(cat) if quantizer is None else QuantLinear.from_linear(cat, quantizer, layout=layout, **_compute_kw(layout))
     fused = FusedProjections(proj, [l.out_features for l in lins])
     for i, n in enumerate(names):
         setattr(parent, n, ProjectionSlice(fused, i, owner=(i == 0)))
@@ -840,7 +860,7 @@ def make_quant(module, quantizers, name='', layout="auto", fuse=None):
     ``fuse``: groups of sibling names, e.g. ``[("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj")]``: wherever a
     module has all the Linears of a group as children (all listed in `quantizers`, with equal quantiser settings and blocks
     along in_features, or all None) they are packed as ONE weight (fuse_projections): one GEMM launch instead of two or
-    three, the same values."""
+    three, the same values.  ``layout="compact"`` (MSQ-C1; int2 / fp4 formats, block 16 / 32) quantises in float32."""
     children = dict(module.named_children())
     for group in (fuse or ()):
         if not all(g in children and isinstance(children[g], nn.Linear) for g in group):
@@ -872,7 +892,7 @@ def make_quant(module, quantizers, name='', layout="auto", fuse=None):
             if quantizers[full] is None:
                 setattr(module, attr, QuantLinear.from_dense(child))
             else:
-                setattr(module, attr, QuantLinear.from_linear(child, quantizers[full], layout=layout))
+                setattr(module, attr, QuantLinear.from_linear(child, quantizers[full], layout=layout, **_compute_kw(layout)))
         elif not isinstance(child, (ProjectionSlice, QuantLinear, MXLinearW4A8)):
             make_quant(child, quantizers, full, layout, fuse)
     return module
@@ -927,10 +947,11 @@ class RowParallelQuantLinear(nn.Module):
         return rank * per, (rank + 1) * per
 
     @classmethod
-    def from_linear(cls, linear, quantizer, world_size, rank, process_group=None, path="bf16", **kw):
+    def from_linear(cls, linear, quantizer, world_size, rank, process_group=None, path="bf16", layout=None, **kw):
         """Quantise and pack this rank's K slice of a dense Linear.  ``path="bf16"``: fused dequant-GEMM shard
         (QuantLinear); ``"mx"``: the fake-quant values as an exact e4m3 operand with MX-FP8 activations
-        (MXLinearW4A8.from_values).  Blocks run along K, so every shard's masks and scales equal the unsharded ones."""
+        (MXLinearW4A8.from_values).  Blocks run along K, so every shard's masks and scales equal the unsharded ones.
+        ``layout`` (bf16 path): packed layout of the shard, e.g. "compact" (float32 compute); None = QuantLinear.from_linear's default."""
         k0, k1 = cls.shard_bounds(linear.in_features, world_size, rank, quantizer.block_size, 128 if path == "mx" else 64)
         has_bias = linear.bias is not None and rank == 0
         Wl = linear.weight.data[:, k0:k1].contiguous()
@@ -950,7 +971,8 @@ class RowParallelQuantLinear(nn.Module):
                 local.weight.copy_(Wl)
                 if has_bias:
                     local.bias.copy_(linear.bias)
-            shard = QuantLinear.from_linear(local, quantizer, out_dtype=kw["reduce_dtype"])
+            lkw = {} if layout is None else dict(layout=layout, compute_dtype="float32" if layout == "compact" else "input")
+            shard = QuantLinear.from_linear(local, quantizer, out_dtype=kw["reduce_dtype"], **lkw)
         else:
             raise MsqError("RowParallelQuantLinear.from_linear: path must be 'bf16' or 'mx'")
         return cls(shard, world_size, rank, process_group, **kw)

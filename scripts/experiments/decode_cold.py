@@ -2,7 +2,10 @@
 """Decode (M = 1 ... 16) time of the fused Llama-2-7B projections with COLD weights: every graph walks through enough distinct
 copies of the packed weight (>= 1 GB) that neither the L2 nor the 256 MB Infinity Cache can hold them -- what a decode step
 over 32 layers sees (a graph replaying ONE weight measures the Infinity Cache instead).
-Usage: python scripts/experiments/decode_cold.py [fp8|posit] [M ...]"""
+Usage: python scripts/experiments/decode_cold.py [fp8|posit|mx8|mx4|c16|u16|c32|u32] [M ...]
+c16 / c32: int2 inliers + fp4 outliers at block 16 / 32 in the compact layout (MSQ-C1, 6.0 / 5.5 bits per weight); u16 / u32: the same weight and
+formats in the unified layout (8.25 bits).  When both of a pair are asked for, their time ratio is printed per projection and M, and with
+PACK=1 the pack kernels' time for W[16384, 4096] in both layouts."""
 import os
 import sys
 
@@ -14,7 +17,8 @@ from msq import qlinear
 
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
-fmts = [a for a in sys.argv[1:] if a in ("fp8", "posit", "mx8", "mx4")] or ["fp8", "posit"]      # mx8 / mx4: the MX matrix path (e4m3 values / plain MX-FP4 operand)
+LOWBIT = {"c16": ("compact", 16), "u16": ("unified", 16), "c32": ("compact", 32), "u32": ("unified", 32)}      # int2 / fp4: (layout, block)
+fmts = [a for a in sys.argv[1:] if a in ("fp8", "posit", "mx8", "mx4") or a in LOWBIT] or ["fp8", "posit"]      # mx8 / mx4: the MX matrix path (e4m3 values / plain MX-FP4 operand)
 Ms = [int(a) for a in sys.argv[1:] if a.isdigit()] or [1, 16]
 FO = {"fp8": "fp8_e4m3", "posit": "posit8_es1"}
 
@@ -50,8 +54,25 @@ def tgraph(fns, reps=5):
     return e0.elapsed_time(e1) / reps / len(fns) * 1e3
 
 
+def pack_times(reps=5):
+    """device time of pack_weight's launches for W[16384, 4096], int2 / fp4, compact beside unified (same weight, same run)"""
+    W = torch.randn(16384, 4096, device=dev) * 0.02
+    W[torch.rand(16384, 4096, device=dev) < 0.005] *= 16
+    for f in [f for f in fmts if f in LOWBIT]:
+        lay, bs = LOWBIT[f]
+        ts = []
+        for _ in range(reps + 1):
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            P = qlinear._pack(W, 8, 8, "int2", "fp4", 2, bs, "nearest", False, 0, lay)
+            e1.record(); torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3)
+        print(f"pack W[16384, 4096] int2/fp4 block {bs} {lay:8s}: {min(ts[1:]):7.1f} us (best of {reps}; buffer allocation and the status read-back included), {P.nbytes/1e6:.1f} MB", flush=True)
+
+
 def main():
     tot = {}
+    res = {}
     ONLY = [a for a in os.environ.get("ONLY", "").split(",") if a]
     for (name, N, K) in (("qkv", 12288, 4096), ("o", 4096, 4096), ("gate_up", 22016, 4096), ("down", 4096, 11008)):
         if ONLY and name not in ONLY:
@@ -63,6 +84,8 @@ def main():
                 P0 = qlinear.mx_pack_values(msq.quant.outlier_fakequant(W[:, :K // 128 * 128].contiguous(), 8, 8, "fp4_e2m1", "fp8_e4m3", 2, -1, 32)["out"])
             elif f == "mx4":
                 P0 = qlinear.mx_pack_weight(W[:, :K // 128 * 128].contiguous())
+            elif f in LOWBIT:
+                P0 = qlinear.pack_weight(W, 8, 8, "int2", "fp4", 2, LOWBIT[f][1], layout=LOWBIT[f][0])
             else:
                 P0 = qlinear.pack_weight(W, 8, 8, "fp4_e2m1", FO[f], 2, 32, layout="unified")
             call = qlinear.qlinear_mx_w4a8 if f in ("mx8", "mx4") else qlinear.qlinear
@@ -72,8 +95,14 @@ def main():
                 X = torch.randn(M, P0.k, device=dev).to(torch.bfloat16)
                 us = tgraph([(lambda P=P: call(X, P)) for P in Ps])
                 tot[(f, M)] = tot.get((f, M), 0.0) + us
+                res[(name, f, M)] = (us, P0.nbytes)
                 print(f"{name:8s} N{N:6d} K{K:6d} {f:5s} M{M:3d}: {us:6.1f} us  {P0.nbytes/us/1e3:5.0f} GB/s of packed weight ({copies} copies, {P0.nbytes/1e6:.0f} MB each)", flush=True)
             del Ps
+        for c, u in (("c16", "u16"), ("c32", "u32")):
+            for M in Ms:
+                if (name, c, M) in res and (name, u, M) in res:
+                    (tc, bc), (tu, bu) = res[(name, c, M)], res[(name, u, M)]
+                    print(f"{name:8s} {c} / {u} M{M:3d}: time ratio {tc/tu:5.3f}  (byte ratio {bc/bu:5.3f})", flush=True)
         if os.environ.get("DENSE", "0") == "1":
             Wb = W.to(torch.bfloat16)
             copies = max(4, int(1.2e9 // (N * K * 2)) + 1)
@@ -86,6 +115,8 @@ def main():
         del W
     for k, v in sorted(tot.items()):
         print(f"layer total {k[0]} M{k[1]}: {v:6.1f} us")
+    if os.environ.get("PACK", "0") == "1":
+        pack_times()
 
 
 if __name__ == "__main__":
