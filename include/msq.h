@@ -83,12 +83,17 @@ extern "C" {
 #define MSQ_PLANE_SEL 7  /* compact (with in_kind FP4): the out plane holds ONE SELECT BIT per weight; the weight's
                             e2m1 nibble in the inlier plane is scaled by the outlier scale where the bit is set
                             (outlier formats fp4_e2m1, int2: values on the e2m1 grid themselves)    */
+#define MSQ_PLANE_U6 8   /* unified, 6 bits (in_kind NONE): the top six bits `s eeee m` of the MSQ-U1 e4m3 byte of every weight, split into a
+                            high-nibble plane (passed as inl_plane) and a low-pair plane (out_plane); the scale plane is MSQ-U1's.
+                            Holds values of ONE significant mantissa bit (int2 / fp4_e2m1 values, any block axis, any quantiser)  */
 
 /* packed layouts */
 #define MSQ_LAYOUT_PLANES 0  /* "MSQ-T1": inlier plane + outlier plane + two scales per block          */
 #define MSQ_LAYOUT_UNIFIED 1 /* "MSQ-U1": one 8-bit code plane (+ extension bits) + one scale per 32 k */
 #define MSQ_LAYOUT_COMPACT 2 /* "MSQ-C1": one e2m1 nibble + one select bit per weight + two scales per block (int2 / fp4 inliers with
                                 int2 / fp4 outliers, block 16 or 32): 6.0 / 5.5 bits per weight                  */
+#define MSQ_LAYOUT_UNIFIED6 3 /* "MSQ-U6": the top six bits of the MSQ-U1 code + one scale per 32 k (formats of one significant
+                                mantissa bit: int2 / fp4_e2m1 inliers and outliers): 6.25 bits per weight               */
 
 int msq_version(void);
 const char* msq_last_error(void);
@@ -236,9 +241,27 @@ int msq_outlier_fakequant(const void* in, void* out, uint8_t* mask, float* e_in,
  * is set; the pack kernel runs the same instruction sequence on every code and raises MSQ_STATUS_INEXACT if a value
  * does not come back (intermediate or result outside the normal bf16 range, scale byte outside 1..254).  The packer
  * builds it for variant 0 with round-to-nearest in one fused pass; other configurations return MSQ_ERR_UNSUPPORTED.
+ *
+ * Six-bit unified layout ("MSQ-U6", MSQ_PLANE_U6 with in_kind NONE): int2 and fp4_e2m1 values have one significant
+ * mantissa bit, so their MSQ-U1 code `s eeee mmm` has its two low mantissa bits clear (down to the e4m3 subnormal 2^-7
+ * times the scale; 2^-8 and 2^-9 times the scale need them and do not fit).  The layout stores the top six bits of the
+ * MSQ-U1 byte of every weight and MSQ-U1's scale plane unchanged -- whatever axis the quantiser's blocks ran along,
+ * whatever the block size, whichever quantiser (RTN, GPTQ, in-dtype) made the values.  With c[0..7] the eight MSQ-U1
+ * code dwords of a lane and half tile kf (c[2 nf + h] = dword h of fragment nf):
+ *   high-nibble plane (inl_plane): per tile 2 slots (kf) of 64 lanes x 16 B (the shape of the MSQ-T1 inlier plane);
+ *                  dword d = (c[2 d] & 0xF0F0F0F0) | ((c[2 d + 1] & 0xF0F0F0F0) >> 4)
+ *   low-pair plane (out_plane): per tile 2 slots (kf) of 64 lanes x 8 B; dword e = OR over i = 0..3 of
+ *                  rotl(c[4 e + i] & 0x0C0C0C0C, 2 i) (the four rotated masks tile the 32 bits exactly)
+ *   scale plane  : as MSQ-U1 (16 groups x 8 B per tile)
+ * = tiles * (2048 + 1024 + 128) bytes: 6.25 bits per weight.  Decode of code dword i: (H[i >> 1] << 4 (i & 1)) &
+ * 0xF0F0F0F0, OR rotr(L[i >> 2], 2 (i & 3)) & 0x0C0C0C0C -- then MSQ-U1's convert.  Zero is +0 (a -0 input is stored as
+ * +0).  msq_pack_values and the fused packer encode as for MSQ-U1 (same scale rule), run this decode on every code and
+ * raise MSQ_STATUS_INEXACT when a code needs its two low bits or a value does not come back.  msq_packed_kinds_layout
+ * returns the kind for formats of one significant mantissa bit only; the fused packer has MSQ-U1's limits (variant 0,
+ * round-to-nearest, block <= 64).
  * ------------------------------------------------------------------------- */
 int msq_packed_kinds(int inlier_fmt, int outlier_fmt, int* in_kind, int* out_kind);
-/* layout-aware form; MSQ_ERR_UNSUPPORTED when the formats cannot use the unified / compact layout */
+/* layout-aware form; MSQ_ERR_UNSUPPORTED when the formats cannot use the unified / compact / six-bit unified layout */
 int msq_packed_kinds_layout(int inlier_fmt, int outlier_fmt, int layout, int* in_kind, int* out_kind);
 int msq_packed_sizes(int64_t N, int64_t K, int block, int in_kind, int out_kind, int64_t* inl_bytes,
                      int64_t* out_bytes, int64_t* scale_bytes, int64_t* workspace_bytes);
@@ -253,8 +276,9 @@ int msq_outlier_pack(const float* W, void* inl_plane, void* out_plane, void* sca
 
 /* pack a dense tensor that already holds fake-quant VALUES (any quantiser: blocks along out_features as
  * in the reference harness default llm/llama.py:229-237, the GPTQ solver's output llm/gptq.py:166, ...) into a
- * single-plane kind with in_kind MSQ_PLANE_NONE: MSQ_PLANE_U8, MSQ_PLANE_U8X or MSQ_PLANE_BF16.  Nothing is
- * rounded: MSQ_STATUS_INEXACT is raised if a value does not fit the kind (callers try U8, U8X, BF16 in turn). */
+ * single-plane kind with in_kind MSQ_PLANE_NONE: MSQ_PLANE_U6, MSQ_PLANE_U8, MSQ_PLANE_U8X or MSQ_PLANE_BF16.  Nothing is
+ * rounded: MSQ_STATUS_INEXACT is raised if a value does not fit the kind (callers try U8, U8X, BF16 in turn; U6 first
+ * when they ask for it: int2 / fp4 values in 6.25 bits per weight). */
 int msq_pack_values(const float* Wq, void* inl_plane, void* out_plane, void* scale_plane, int* status_flag,
                     int64_t N, int64_t K, int in_kind, int out_kind, void* stream);
 

@@ -7,7 +7,7 @@ buffer of the model, and a JSON header in the metadata describing each packed la
 rebuilt without re-quantising (and, for the 70B row-parallel configuration, shard by shard: every rank saves
 and loads its own file, `shard` / `world_size` are recorded).
 
-    header = {"format": "msq-packed", "version": 2 (3 with a compact layer), "shard": r, "world_size": G,
+    header = {"format": "msq-packed", "version": 2 (3 with a compact layer, 4 with a unified6 layer), "shard": r, "world_size": G,
               "layers": {"<module name>": {"in_features", "out_features", "block_size", "layout",
                                             "in_kind", "out_kind", "inlier_elem_format",
                                             "outlier_elem_format", "bias", "out_dtype"}}}
@@ -25,6 +25,9 @@ Version 3: a file that holds a layer in the compact layout (``"layout": "compact
 Only such files are written as version 3 -- a model without a compact layer is written exactly as before (version 2) -- so that a
 build which does not know the layout refuses the file with its "unsupported version" message instead of deriving other kinds;
 read_header accepts version 3 only together with such a layer.
+
+Version 4: a file that holds a layer in the six-bit unified layout (``"layout": "unified6"``, plane kinds (0, 8): MSQ-U6 of include/msq.h), by
+the same rule: written only for such files (which may hold compact layers as well), accepted only together with such a layer.
 """
 import json
 
@@ -36,6 +39,7 @@ from .qlinear import K_MULT, N_MULT, FusedProjections, MXLinearW4A8, ProjectionS
 
 FORMAT, VERSION = "msq-packed", 2
 VERSION_COMPACT = 3                                      # written (and read) only for a file that holds a compact layer
+VERSION_UNIFIED6 = 4                                     # written (and read) only for a file that holds a unified6 layer
 
 
 def _packed_layers(model):
@@ -61,6 +65,10 @@ def _has_compact(layers):
     return any(d.get("layout") == "compact" for d in layers.values())
 
 
+def _has_unified6(layers):
+    return any(d.get("layout") == "unified6" for d in layers.values())
+
+
 def save_packed(model, path, shard=0, world_size=1):
     """Write every tensor of `model` (packed planes included) and the layer table to `path`."""
     from safetensors.torch import save_file
@@ -78,7 +86,7 @@ def save_packed(model, path, shard=0, world_size=1):
                             padded_out=_ceil_to(m.out_features, N_MULT), padded_in=_ceil_to(m.in_features, K_MULT))
     for name, (parent, sibs, splits) in fused.items():            # fused q / k / v or gate / up: one packed weight, several stand-ins
         layers[name]["fused"] = dict(parent=parent, names=sibs, splits=splits)
-    version = VERSION_COMPACT if _has_compact(layers) else VERSION
+    version = VERSION_UNIFIED6 if _has_unified6(layers) else (VERSION_COMPACT if _has_compact(layers) else VERSION)
     header = dict(format=FORMAT, version=version, shard=int(shard), world_size=int(world_size), layers=layers)
     tensors = {k: v.detach().contiguous().cpu() for k, v in model.state_dict().items()}
     save_file(tensors, path, metadata={"msq": json.dumps(header)})
@@ -94,10 +102,13 @@ def read_header(path):
     header = json.loads(meta["msq"])
     version = int(header.get("version", -1))
     # version 3 is defined by its compact layer: a "version 3" header without one comes from some other definition of that number
-    known = version <= VERSION or (version == VERSION_COMPACT and _has_compact(header.get("layers") or {}))
+    # ... and version 4 by its unified6 layer
+    layers = header.get("layers") or {}
+    known = version <= VERSION or (version == VERSION_COMPACT and _has_compact(layers)) or (version == VERSION_UNIFIED6 and _has_unified6(layers))
     if header.get("format") != FORMAT or not known:
-        raise MsqError("unsupported checkpoint format %r version %r (this build reads %s versions 1..%d, and version %d files that hold a compact layer)"
-                       % (header.get("format"), header.get("version"), FORMAT, VERSION, VERSION_COMPACT))
+        raise MsqError("unsupported checkpoint format %r version %r (this build reads %s versions 1..%d, version %d files that hold a compact layer "
+                       "and version %d files that hold a unified6 layer)"
+                       % (header.get("format"), header.get("version"), FORMAT, VERSION, VERSION_COMPACT, VERSION_UNIFIED6))
     return header
 
 

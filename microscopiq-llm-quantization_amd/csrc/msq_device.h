@@ -416,6 +416,26 @@ MSQ_D uint32_t sel_dword(uint32_t nib, float s_in, int d, uint32_t sel, int sh, 
     const uint32_t m = (sel >> sh) & 0x00010001u;
     return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2_t, m) * __builtin_bit_cast(u16x2_t, step) + __builtin_bit_cast(u16x2_t, r));   // v_pk_mad_u16
 }
+
+// ---------------------------------------------------------------------------
+// MSQ-U6 (six-bit unified layout, include/msq.h) decode of MSQ-U1 code dword i (0..7: dword i & 1 of fragment i >> 1) of a lane's half
+// tile: `hi` = dword i >> 1 of the high-nibble slot (even code dwords in the high nibble of every byte, odd ones in the low nibble),
+// `lo` = dword i >> 2 of the low-pair slot (code dword 4 e + j contributes its bits 2..3 of every byte, rotated left by 2 j).  The two
+// low bits of every code byte come back as zero.  3-4 vector instructions per code dword: (shift,) and, rotate (v_alignbit; none for
+// i & 3 == 0), v_and_or.  The pack kernel proves every code with this very function (k_pack_tile_u), the GEMMs decode with it.
+// ---------------------------------------------------------------------------
+MSQ_D uint32_t u6_hi(uint32_t c_even, uint32_t c_odd) { return (c_even & 0xF0F0F0F0u) | ((c_odd & 0xF0F0F0F0u) >> 4); }
+MSQ_D uint32_t u6_lo(uint32_t c, int i) {                   // contribution of code dword i to its low-pair dword
+    const uint32_t m = c & 0x0C0C0C0Cu;
+    const int r = 2 * (i & 3);
+    return r ? __builtin_amdgcn_alignbit(m, m, 32 - r) : m;
+}
+MSQ_D uint32_t u6_code(uint32_t hi, uint32_t lo, int i) {
+    const uint32_t h = ((i & 1) ? (hi << 4) : hi) & 0xF0F0F0F0u;
+    const int r = 2 * (i & 3);
+    const uint32_t l = r ? __builtin_amdgcn_alignbit(lo, lo, r) : lo;
+    return (l & 0x0C0C0C0Cu) | h;
+}
 #endif
 
 }  // namespace msq

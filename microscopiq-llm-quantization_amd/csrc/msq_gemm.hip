@@ -107,6 +107,16 @@ MSQ_D void load_tile(TileRegs& t, const uint8_t* inl_plane, const uint8_t* out_p
             t.ext[0] = *reinterpret_cast<const uint32_t*>(inl_plane + ((tile * 2 + 0) * 64 + lane) * 4);
             t.ext[1] = *reinterpret_cast<const uint32_t*>(inl_plane + ((tile * 2 + 1) * 64 + lane) * 4);
         } else { t.ext[0] = 0; t.ext[1] = 0; }
+        if (OUT_KIND == MSQ_PLANE_U6) {    // high-nibble slots (2 x 64 lanes x 16 B, passed as inl_plane) and low-pair slots (2 x 64 lanes x 8 B): the weight stream
+#pragma unroll
+            for (int kf = 0; kf < 2; ++kf) {
+                const u32x4_t* hp = reinterpret_cast<const u32x4_t*>(inl_plane + ((tile * 2 + kf) * 64 + lane) * 16);
+                const u32x2_t* lp = reinterpret_cast<const u32x2_t*>(out_plane + ((tile * 2 + kf) * 64 + lane) * 8);
+                t.inl[kf] = NT ? __builtin_nontemporal_load(hp) : *hp;
+                const u32x2_t l = NT ? __builtin_nontemporal_load(lp) : *lp;
+                t.out[0][kf * 2] = l[0]; t.out[0][kf * 2 + 1] = l[1];
+            }
+        }
     } else if (IN_KIND != MSQ_PLANE_NONE) {
 #pragma unroll
         for (int kf = 0; kf < 2; ++kf)     // (compact layout: the nibble plane IS the weight stream, read once like the code slots below)
@@ -234,7 +244,7 @@ k_qgemm3(const uint16_t* __restrict__ X, const uint8_t* __restrict__ inl_plane, 
     const int64_t ntiles = (int64_t)(N / TILE_N) * KT;
     PlaneRsrc pr;
     pr.inl = make_rsrc(inl_plane, ntiles * 2 * (OUT_KIND == MSQ_PLANE_U8X ? 256 : 1024));
-    pr.out = make_rsrc(out_plane, OUT_KIND == MSQ_PLANE_SEL ? ntiles * 2 * 256 : ntiles * 2 * HalfSlots<OUT_KIND>::n * 1024);
+    pr.out = make_rsrc(out_plane, OUT_KIND == MSQ_PLANE_SEL ? ntiles * 2 * 256 : (OUT_KIND == MSQ_PLANE_U6 ? ntiles * 2 * 512 : ntiles * 2 * HalfSlots<OUT_KIND>::n * 1024));
     constexpr bool HAS_SCALE = HasScale<IN_KIND, OUT_KIND>::v;
     constexpr int SCLB = SclBytes<OUT_KIND>::n;               // scale bytes per lane group and tile
     pr.scl = make_rsrc(scl_plane, ntiles * scl_groups * SCLB);
@@ -984,6 +994,8 @@ k_qgemv(const uint16_t* __restrict__ X, const uint8_t* __restrict__ inl_plane, c
 // (DEEP3: three -- slower with cold weights: more bytes in flight than the DRAM pages like, see the launcher).
 // OUT_KIND = MSQ_PLANE_SEL (compact layout MSQ-C1; `ext_plane` = the nibble plane, `code_plane` = the select bits): per tile a wave loads
 // two nibble slots (16 B per lane), two select dwords and the 16 scale bytes of its lane group: 2560 + 256 / 512 B per tile instead of 4224.
+// OUT_KIND = MSQ_PLANE_U6 (six-bit unified layout MSQ-U6; `ext_plane` = the high-nibble plane, `code_plane` = the low pairs): per tile a wave
+// loads two high-nibble slots (16 B per lane), two low-pair slots (8 B per lane) and the MSQ-U1 scale pair: 3200 B per tile instead of 4224.
 // Half strips over all of K for the 4096-wide projections (128 blocks) were built and measured slower than the split-K planes
 // of k_qgemv (down projection 14.7 -> 17.3 us): a CU keeps only so many bytes in flight, 128 CUs cannot pull what 256 can.
 // ---------------------------------------------------------------------------
@@ -994,6 +1006,7 @@ k_qgemv_u(const uint16_t* __restrict__ X, const uint8_t* __restrict__ ext_plane,
           int y_kind, int x_f16, int scl_groups) {
     constexpr bool EXT = (OUT_KIND == MSQ_PLANE_U8X);
     constexpr bool SEL = (OUT_KIND == MSQ_PLANE_SEL);
+    constexpr bool U6 = (OUT_KIND == MSQ_PLANE_U6);
     constexpr int NFB = 4;                                       // 16-column fragments per block
     constexpr int R = MG * NFB * 4;                              // results per lane
     extern __shared__ __attribute__((aligned(16))) char smem_u[];
@@ -1019,7 +1032,7 @@ k_qgemv_u(const uint16_t* __restrict__ X, const uint8_t* __restrict__ ext_plane,
 #pragma unroll
     for (int j = 0; j < MG; ++j) { int m = j * 16 + c; m = m < M ? m : M - 1; xrow[j] = X + (int64_t)m * K + g * 8; }
 
-    struct UT { u32x4_t code[2][SEL ? 1 : 2]; uint32_t scl[SEL ? 4 : 2]; uint32_t ext[2]; };   // SEL: nibble slot, scale dword nf, select dwords
+    struct UT { u32x4_t code[2][(SEL || U6) ? 1 : 2]; uint32_t scl[SEL ? 4 : 2]; uint32_t ext[2]; u32x2_t lo[U6 ? 2 : 1]; };   // SEL: nibble slot, scale dword nf, select dwords; U6: high-nibble slot, low pairs
     struct XF { u32x4_t v[2][MG]; };
     auto load_u = [&](UT& t, int kt) {
         const int64_t tile = tile_row + kt;
@@ -1031,6 +1044,16 @@ k_qgemv_u(const uint16_t* __restrict__ X, const uint8_t* __restrict__ ext_plane,
             }
             const u32x4_t sc = *reinterpret_cast<const u32x4_t*>(scl_plane + (tile * scl_groups + scl_group(lane, scl_groups)) * 16);
             t.scl[0] = sc[0]; t.scl[1] = sc[1]; t.scl[2] = sc[2]; t.scl[3] = sc[3];
+            return;
+        }
+        if constexpr (U6) {
+#pragma unroll
+            for (int kf = 0; kf < 2; ++kf) {
+                t.code[kf][0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(ext_plane + ((tile * 2 + kf) * 64 + lane) * 16));
+                t.lo[kf] = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(code_plane + ((tile * 2 + kf) * 64 + lane) * 8));
+            }
+            const uint2 sc = *reinterpret_cast<const uint2*>(scl_plane + (tile * 16 + c) * 8);
+            t.scl[0] = sc.x; t.scl[1] = sc.y;
             return;
         }
 #pragma unroll
@@ -1080,6 +1103,7 @@ k_qgemv_u(const uint16_t* __restrict__ X, const uint8_t* __restrict__ ext_plane,
             for (int nf = 0; nf < NFB; ++nf) {
                 bf16x8_t wf;
                 if constexpr (SEL) wf = __builtin_bit_cast(bf16x8_t, dequant_frag_sel(cur.code[kf][0][nf], cur.ext[kf], cur.scl[nf] >> (16 * kf), nf));
+                else if constexpr (U6) wf = __builtin_bit_cast(bf16x8_t, dequant_frag_u6(cur.code[kf][0], cur.lo[kf][0], cur.lo[kf][1], scale_operand(cur.scl[kf], nf), nf));
                 else {
                     const u32x4_t o = cur.code[kf][nf >> 1];
                     wf = __builtin_bit_cast(bf16x8_t, dequant_frag_unified<OUT_KIND>(o[(nf & 1) * 2], o[(nf & 1) * 2 + 1],
@@ -1257,7 +1281,7 @@ static int sig_bits(const msq_host::FmtInfo& f, int fmt_id) {
 
 int msq_packed_kinds_layout(int inlier_fmt, int outlier_fmt, int layout, int* in_kind, int* out_kind) {
     if (layout == MSQ_LAYOUT_PLANES) return msq_packed_kinds(inlier_fmt, outlier_fmt, in_kind, out_kind);
-    if (layout != MSQ_LAYOUT_UNIFIED && layout != MSQ_LAYOUT_COMPACT) return fail2(MSQ_ERR_BAD_ARG, "msq_packed_kinds_layout: bad layout");
+    if (layout != MSQ_LAYOUT_UNIFIED && layout != MSQ_LAYOUT_COMPACT && layout != MSQ_LAYOUT_UNIFIED6) return fail2(MSQ_ERR_BAD_ARG, "msq_packed_kinds_layout: bad layout");
     msq_host::FmtInfo fi, fo;
     if (!msq_host::format_info(inlier_fmt, &fi) || !msq_host::format_info(outlier_fmt, &fo))
         return fail2(MSQ_ERR_BAD_ARG, "msq_packed_kinds_layout: unknown element format");
@@ -1272,6 +1296,13 @@ int msq_packed_kinds_layout(int inlier_fmt, int outlier_fmt, int layout, int* in
     }
     const int si = sig_bits(fi, inlier_fmt), so = sig_bits(fo, outlier_fmt);
     const int sg = si > so ? si : so;
+    if (layout == MSQ_LAYOUT_UNIFIED6) {                       // the top six bits of the e4m3 code: one significant mantissa bit (implicit one + 1)
+        if (fi.kind != 0 || fo.kind != 0 || sg > 2)
+            return fail2(MSQ_ERR_UNSUPPORTED, "msq_packed_kinds_layout: the six-bit unified layout holds formats of one significant mantissa bit only (int2 / fp4_e2m1 inliers and outliers; other formats keep the unified or the two-plane layout)");
+        if (in_kind) *in_kind = MSQ_PLANE_NONE;
+        if (out_kind) *out_kind = MSQ_PLANE_U6;
+        return MSQ_OK;
+    }
     if (fi.kind != 0 || sg > 5)
         return fail2(MSQ_ERR_UNSUPPORTED, "msq_packed_kinds_layout: the unified layout holds float/int inliers and values of at most 5 significant bits");
     if (in_kind) *in_kind = MSQ_PLANE_NONE;
@@ -1293,6 +1324,14 @@ int msq_packed_sizes(int64_t N, int64_t K, int block, int in_kind, int out_kind,
         if (inl_bytes) *inl_bytes = tiles * 2 * 1024;
         if (out_bytes) *out_bytes = tiles * 2 * 256;
         if (scale_bytes) *scale_bytes = tiles * (block == 16 ? 32 : 16) * 16;
+        if (workspace_bytes) *workspace_bytes = 0;
+        return MSQ_OK;
+    }
+    if (out_kind == MSQ_PLANE_U6) {                            // six-bit unified layout: high-nibble plane (as inl_plane) + low-pair plane + the MSQ-U1 scale plane
+        if (in_kind != MSQ_PLANE_NONE) return fail2(MSQ_ERR_BAD_ARG, "msq_packed_sizes: unified planes have no inlier plane");
+        if (inl_bytes) *inl_bytes = tiles * 2 * 1024;
+        if (out_bytes) *out_bytes = tiles * 2 * 512;
+        if (scale_bytes) *scale_bytes = tiles * 16 * 8;
         if (workspace_bytes) *workspace_bytes = 0;
         return MSQ_OK;
     }
@@ -1344,6 +1383,14 @@ int msq_outlier_pack(const float* W, void* inl_plane, void* out_plane, void* sca
         if (rc == MSQ_ERR_UNSUPPORTED) return fail2(rc, "msq_outlier_pack: the unified layout needs nearest rounding and block <= 64");
         return rc;
     }
+    if (layout == MSQ_LAYOUT_UNIFIED6) {
+        if (!scale_plane || !inl_plane) return fail2(MSQ_ERR_BAD_ARG, "msq_outlier_pack: null buffer");
+        if (variant != MSQ_VARIANT_QUANT) return fail2(MSQ_ERR_UNSUPPORTED, "msq_outlier_pack: the six-bit unified layout packs the canonical quantiser (variant 0) only");
+        rc = msq_pack_fused_(W, inl_plane, out_plane, scale_plane, status_flag, N, K, block, inlier_fmt, outlier_fmt,
+                             inlier_scale_bits, outlier_scale_bits, std_dev, rmode, flush_fp32_subnorms, ik, ok, stream);
+        if (rc == MSQ_ERR_UNSUPPORTED) return fail2(rc, "msq_outlier_pack: the six-bit unified layout needs nearest rounding and block <= 64");
+        return rc;
+    }
     if (layout == MSQ_LAYOUT_COMPACT) {
         if (variant != MSQ_VARIANT_QUANT) return fail2(MSQ_ERR_UNSUPPORTED, "msq_outlier_pack: the compact layout packs the canonical quantiser (variant 0) only");
         rc = msq_pack_fused_(W, inl_plane, out_plane, scale_plane, status_flag, N, K, block, inlier_fmt, outlier_fmt,
@@ -1392,10 +1439,10 @@ int msq_pack_values(const float* Wq, void* inl_plane, void* out_plane, void* sca
                     int64_t K, int in_kind, int out_kind, void* stream) {
     int rc = msq_packed_sizes(N, K, 32, in_kind, out_kind, nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
-    if (in_kind != MSQ_PLANE_NONE) return fail2(MSQ_ERR_UNSUPPORTED, "msq_pack_values: only single-plane kinds (U8, U8X, BF16 with in_kind NONE)");
+    if (in_kind != MSQ_PLANE_NONE) return fail2(MSQ_ERR_UNSUPPORTED, "msq_pack_values: only single-plane kinds (U6, U8, U8X, BF16 with in_kind NONE)");
     if (!Wq || !out_plane) return fail2(MSQ_ERR_BAD_ARG, "msq_pack_values: null buffer");
-    if (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X) {
-        if (!scale_plane || (out_kind == MSQ_PLANE_U8X && !inl_plane)) return fail2(MSQ_ERR_BAD_ARG, "msq_pack_values: null buffer");
+    if (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X || out_kind == MSQ_PLANE_U6) {
+        if (!scale_plane || (out_kind != MSQ_PLANE_U8 && !inl_plane)) return fail2(MSQ_ERR_BAD_ARG, "msq_pack_values: null buffer");
         return msq_pack_values_u_(Wq, inl_plane, out_plane, scale_plane, status_flag, N, K, out_kind, stream);
     }
     if (out_kind != MSQ_PLANE_BF16) return fail2(MSQ_ERR_UNSUPPORTED, "msq_pack_values: unsupported plane kind");
@@ -1411,7 +1458,7 @@ int msq_outlier_unpack(const void* inl_plane, const void* out_plane, const void*
     if (rc) return rc;
     if (!out_plane || !W_out || (in_kind != MSQ_PLANE_NONE && (!inl_plane || !scale_plane)))
         return fail2(MSQ_ERR_BAD_ARG, "msq_outlier_unpack: null buffer");
-    if ((out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X) && (!scale_plane || (out_kind == MSQ_PLANE_U8X && !inl_plane)))
+    if ((out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X || out_kind == MSQ_PLANE_U6) && (!scale_plane || (out_kind != MSQ_PLANE_U8 && !inl_plane)))
         return fail2(MSQ_ERR_BAD_ARG, "msq_outlier_unpack: null buffer");
     if (out_dtype != 0 && out_dtype != 2) return fail2(MSQ_ERR_UNSUPPORTED, "msq_outlier_unpack: out_dtype must be 0 (f32) or 2 (bf16)");
     const int64_t tiles = (N / TILE_N) * (K / TILE_K);
@@ -1430,6 +1477,7 @@ int msq_outlier_unpack(const void* inl_plane, const void* out_plane, const void*
     else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8) MSQ_UP(MSQ_PLANE_NONE, MSQ_PLANE_U8);
     else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8X) MSQ_UP(MSQ_PLANE_NONE, MSQ_PLANE_U8X);
     else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_SEL) MSQ_UP(MSQ_PLANE_FP4, MSQ_PLANE_SEL);
+    else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U6) MSQ_UP(MSQ_PLANE_NONE, MSQ_PLANE_U6);
     else return fail2(MSQ_ERR_UNSUPPORTED, "msq_outlier_unpack: unsupported plane kinds");
 #undef MSQ_UP
     return check_launch2("msq_outlier_unpack");
@@ -1695,6 +1743,10 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
     const bool unified = (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X);
     if (unified && (!scale_plane || (out_kind == MSQ_PLANE_U8X && !inl_plane)))
         return fail2(MSQ_ERR_BAD_ARG, "msq_qlinear_bf16: null buffer");
+    // six-bit unified layout: routed as the compact layout is (k_qgemv_u / k_qgemv + reduce / k_qgemm3), NOT as `unified` -- the hand-scheduled
+    // kernels and the unified-only block shapes have no instantiation for it
+    const bool u6 = (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U6);
+    if (u6 && (!scale_plane || !inl_plane)) return fail2(MSQ_ERR_BAD_ARG, "msq_qlinear_bf16: null buffer");
     if (y_dtype != 0 && y_dtype != 1 && y_dtype != 2) return fail2(MSQ_ERR_UNSUPPORTED, "msq_qlinear_bf16: y_dtype must be 0 (f32), 1 (fp16) or 2 (bf16)");
     if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return fail2(MSQ_ERR_UNSUPPORTED, "msq_qlinear_bf16: dimension too large");
     {   // activations and packed planes are addressed with 32-bit buffer offsets (make_rsrc clamps num_records)
@@ -1706,7 +1758,7 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
     hipStream_t st0 = (hipStream_t)stream;
     const int y16 = (y_dtype == 1) ? 1 : 0;                       // fp16 output: the 16-bit kernels with the half conversion
     const bool compact = (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_SEL);
-    const int groups0 = unified ? 16 : (compact ? (block < 32 ? 32 : 16) : (block < 32 ? 64 : 16));
+    const int groups0 = (unified || u6) ? 16 : (compact ? (block < 32 ? 32 : 16) : (block < 32 ? 64 : 16));
     // fp16 activations are converted inside the decode kernels only: where the bf16 call takes k_qgemm_sk the caller casts (one kernel, one
     // summation order for both activation dtypes: tests/test_gpu_n2_gemm.py::test_decode_kernels_take_fp16_activations)
     if (x_f16 && sk_rule(M, N, K, unified, out_kind))
@@ -1723,7 +1775,7 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
         const int nks = kcd ? 1 : (int)(((K / BK + kc - 1) / kc + 3) / 4);    // partial planes: one per four k-chunks
         // unified layouts, M <= 32, more than 128 strips: the single-launch kernel (MSQ_GEMV_U=0: the earlier kernels, tuning only)
         static const int gvu = [] { const char* e = getenv("MSQ_GEMV_U"); return e ? atoi(e) : 1; }();
-        if (gvu && N / TILE_N > 128 && ((in_kind == MSQ_PLANE_NONE && (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X)) || compact)) {
+        if (gvu && N / TILE_N > 128 && ((in_kind == MSQ_PLANE_NONE && (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X)) || compact || u6)) {
             const int64_t strips = N / TILE_N, KTv = K / TILE_K;
             // Waves per block (= k-runs per strip) so that the grid has ~1000-2000 waves, two tiles in flight each: a COLD read stream
             // is fastest with a few MB in flight (scripts/experiments/hbm_read.hip: 1024 waves x 4 KB reach 6 TB/s, 8192 x 8 KB only
@@ -1744,7 +1796,7 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
             // activation prefetch: from two rows on (one row: every lane reads the same line, an L1 hit), where the registers allow
 #define MSQ_GVUW(OK, WV) do { if (mg == 1) { if (M > 1) MSQ_GVU1(OK, 1, WV, true); else MSQ_GVU1(OK, 1, WV, false); } else if (mg == 2) MSQ_GVU1(OK, 2, WV, false); else MSQ_GVU1(OK, 4, WV, false); } while (0)
 #define MSQ_GVU(OK) do { if (wv == 2) MSQ_GVUW(OK, 2); else if (wv == 4) MSQ_GVUW(OK, 4); else if (wv == 8) MSQ_GVUW(OK, 8); else MSQ_GVUW(OK, 16); } while (0)
-            if (out_kind == MSQ_PLANE_U8) MSQ_GVU(MSQ_PLANE_U8); else if (compact) MSQ_GVU(MSQ_PLANE_SEL); else MSQ_GVU(MSQ_PLANE_U8X);
+            if (out_kind == MSQ_PLANE_U8) MSQ_GVU(MSQ_PLANE_U8); else if (compact) MSQ_GVU(MSQ_PLANE_SEL); else if (u6) MSQ_GVU(MSQ_PLANE_U6); else MSQ_GVU(MSQ_PLANE_U8X);
 #undef MSQ_GVU
 #undef MSQ_GVUW
 #undef MSQ_GVU1
@@ -1771,6 +1823,7 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
             else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8) MSQ_GV(MSQ_PLANE_NONE, MSQ_PLANE_U8);
             else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8X) MSQ_GV(MSQ_PLANE_NONE, MSQ_PLANE_U8X);
             else if (compact) MSQ_GV(MSQ_PLANE_FP4, MSQ_PLANE_SEL);
+            else if (u6) MSQ_GV(MSQ_PLANE_NONE, MSQ_PLANE_U6);
             else return fail2(MSQ_ERR_UNSUPPORTED, "msq_qlinear_bf16: unsupported plane kinds");
 #undef MSQ_GV
 #undef MSQ_GV1
@@ -1835,6 +1888,7 @@ static int qlinear_bf16_impl(const void* X, const void* inl_plane, const void* o
          else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8) MSQ_LAUNCH(KERN, MSQ_PLANE_NONE, MSQ_PLANE_U8); \
          else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U8X) MSQ_LAUNCH(KERN, MSQ_PLANE_NONE, MSQ_PLANE_U8X); \
          else if (in_kind == MSQ_PLANE_FP4 && out_kind == MSQ_PLANE_SEL) MSQ_LAUNCH(KERN, MSQ_PLANE_FP4, MSQ_PLANE_SEL); \
+         else if (in_kind == MSQ_PLANE_NONE && out_kind == MSQ_PLANE_U6) MSQ_LAUNCH(KERN, MSQ_PLANE_NONE, MSQ_PLANE_U6); \
          else return fail2(MSQ_ERR_UNSUPPORTED, "msq_qlinear_bf16: unsupported plane kinds"); } while (0)
     // Eight waves along n (one block of 128 x 512 per CU instead of two of 128 x 256): the eight waves share ONE activation
     // tile, so every wave issues half the LDS-DMA pieces and the CU pulls half the activation bytes from L2 per K-step.
@@ -2291,6 +2345,13 @@ int msq_qlinear_kernel_name(int64_t M, int64_t N, int64_t K, int out_kind, int m
         else snprintf(buf, cap, "k_qgemv<1, 7, %d, 4>", mg);
     }
     else if (out_kind == MSQ_PLANE_SEL && fam == MSQ_KERNEL_GEMM128) snprintf(buf, cap, "k_qgemm3<1, 7, %s>", yt);
+    else if ((out_kind == MSQ_PLANE_U6 || out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X) && fam == MSQ_KERNEL_DECODE) {   // the instantiation itself
+        const int mg = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
+        const int64_t strips = N / TILE_N;
+        if (strips > 128) snprintf(buf, cap, "k_qgemv_u<%d, %d, %d>", out_kind, mg, strips <= 256 ? 8 : (strips <= 640 ? 4 : 2));
+        else snprintf(buf, cap, "k_qgemv<0, %d, %d, %d>", out_kind, mg, (out_kind != MSQ_PLANE_U6 && direct_kc(M, N, K)) ? 16 : 4);
+    }
+    else if (out_kind == MSQ_PLANE_U6 && fam == MSQ_KERNEL_GEMM128) snprintf(buf, cap, "k_qgemm3<0, 8, %s>", yt);
     else if (fam == MSQ_KERNEL_DECODE) snprintf(buf, cap, "k_qgemv_u / k_qgemv<out kind %d>", out_kind);
     else if (fam == MSQ_KERNEL_GEMM128) snprintf(buf, cap, "k_qgemm3<out kind %d, %s>", out_kind, yt);
     else if (fam == MSQ_KERNEL_PERSISTENT) snprintf(buf, cap, "k_qgemm256p<%d, %s>", out_kind, yt);

@@ -87,8 +87,8 @@ MSQ_D float scale_operand(uint32_t d, int idx) {
     return __builtin_bit_cast(float, s);
 }
 
-// unified layout (MSQ-U1): one e4m3 code per weight, one scale per 32 k, optional extension bit
-template <int OUT_KIND> struct IsUnified { static constexpr bool v = (OUT_KIND == MSQ_PLANE_U8 || OUT_KIND == MSQ_PLANE_U8X); };
+// unified layouts (MSQ-U1 / MSQ-U6): one e4m3 code per weight (U6: its top six bits), one scale per 32 k, optional extension bit
+template <int OUT_KIND> struct IsUnified { static constexpr bool v = (OUT_KIND == MSQ_PLANE_U8 || OUT_KIND == MSQ_PLANE_U8X || OUT_KIND == MSQ_PLANE_U6); };
 // does this (in, out) kind pair carry a scale plane?
 template <int IN_KIND, int OUT_KIND> struct HasScale { static constexpr bool v = (IN_KIND != MSQ_PLANE_NONE) || IsUnified<OUT_KIND>::v; };
 
@@ -112,6 +112,13 @@ MSQ_D u32x4_t dequant_frag_unified(uint32_t o0, uint32_t o1, float s, uint32_t e
     return r;
 }
 
+// six-bit unified layout (MSQ-U6): the two MSQ-U1 code dwords of fragment nf out of the half tile's high-nibble slot `hi` and the two
+// dwords (lo0, lo1) of its low-pair slot (u6_code, msq_device.h), then MSQ-U1's converts
+MSQ_D u32x4_t dequant_frag_u6(const u32x4_t& hi, uint32_t lo0, uint32_t lo1, float s, int nf) {
+    const uint32_t lo = (nf >> 1) ? lo1 : lo0;
+    return dequant_frag_unified<MSQ_PLANE_U8>(u6_code(hi[nf], lo, 2 * nf), u6_code(hi[nf], lo, 2 * nf + 1), s, 0u, nf);
+}
+
 // compact layout (MSQ-C1): e2m1 nibble of every weight + select bit; the two scale bytes of the block as (inlier, outlier) pair
 MSQ_D u32x4_t dequant_frag_sel(uint32_t nib, uint32_t sel, uint32_t scale_pair, int nf) {
     const float s_in = __builtin_bit_cast(float, (scale_pair & 0xFFu) << 23);
@@ -127,14 +134,15 @@ MSQ_D int scl_group(int lane, int groups) { return groups == 32 ? ((lane & 15) |
 
 // all 8 fragments of one 64x64 tile for this lane
 struct TileRegs {
-    u32x4_t inl[2];      // [kf]  dword nf
-    u32x4_t out[8];      // 8-bit kinds use [0..3] = (kf*2 + nf/2); bf16 kind uses [kf*4 + nf]
+    u32x4_t inl[2];      // [kf]  dword nf (U6: the high-nibble slot)
+    u32x4_t out[8];      // 8-bit kinds use [0..3] = (kf*2 + nf/2); bf16 kind uses [kf*4 + nf]; U6: [0] = the low-pair dwords kf*2 + e
     u32x4_t scl;         // dword nf: bytes kf*2 + io   (unified: dword kf: byte nf)
     uint32_t ext[2];     // unified U8X: extension bits of half kf; compact (SEL): select bits of half kf
 };
 
 template <int IN_KIND, int OUT_KIND>
 MSQ_D u32x4_t tile_frag(const TileRegs& t, int nf, int kf) {
+    if (OUT_KIND == MSQ_PLANE_U6) return dequant_frag_u6(t.inl[kf], t.out[0][kf * 2], t.out[0][kf * 2 + 1], scale_operand(t.scl[kf], nf), nf);
     if (IsUnified<OUT_KIND>::v) {
         const u32x4_t o = t.out[kf * 2 + (nf >> 1)];
         return dequant_frag_unified<OUT_KIND>(o[(nf & 1) * 2], o[(nf & 1) * 2 + 1], scale_operand(t.scl[kf], nf), t.ext[kf], nf);
@@ -161,7 +169,7 @@ MSQ_D u32x4_t tile_frag(const TileRegs& t, int nf, int kf) {
 MSQ_D int frag_n(int lane, int f) { return f * 16 + (lane & 15); }
 MSQ_D int frag_k(int lane, int kf) { return kf * 32 + (lane >> 4) * 8; }
 
-template <int OUT_KIND> struct OutSlots { static constexpr int n = (OUT_KIND == MSQ_PLANE_BF16) ? 8 : ((OUT_KIND == MSQ_PLANE_SEL) ? 0 : 4); };   // SEL: 2 x 256 B of select bits instead
+template <int OUT_KIND> struct OutSlots { static constexpr int n = (OUT_KIND == MSQ_PLANE_BF16) ? 8 : ((OUT_KIND == MSQ_PLANE_SEL || OUT_KIND == MSQ_PLANE_U6) ? 0 : 4); };   // SEL: 2 x 256 B of select bits instead; U6: 2 x 512 B of low pairs
 // bytes of the scale plane per tile and lane group
 template <int OUT_KIND> struct SclBytes { static constexpr int n = IsUnified<OUT_KIND>::v ? 8 : 16; };
 
@@ -175,10 +183,11 @@ template <int OUT_KIND> struct SclBytes { static constexpr int n = IsUnified<OUT
 // current one (sched_group_barrier pins the interleave), and only one half-step of packed data
 // is in flight per buffer (register budget: 128 acc + 32 wf + <=48 packed + 12 xf).
 // ---------------------------------------------------------------------------
-template <int OUT_KIND> struct HalfSlots { static constexpr int n = (OUT_KIND == MSQ_PLANE_BF16) ? 4 : ((OUT_KIND == MSQ_PLANE_SEL) ? 0 : 2); };
+template <int OUT_KIND> struct HalfSlots { static constexpr int n = (OUT_KIND == MSQ_PLANE_BF16) ? 4 : ((OUT_KIND == MSQ_PLANE_SEL || OUT_KIND == MSQ_PLANE_U6) ? 0 : 2); };
 // vector-memory loads one half-step issues for the packed operand (vmcnt bookkeeping)
 template <int IN_KIND, int OUT_KIND> struct HalfLoads {
-    static constexpr int n = (IN_KIND != MSQ_PLANE_NONE ? 1 : 0) + (((MSQ_ABL & 256) && IsUnified<OUT_KIND>::v) ? 1 : HalfSlots<OUT_KIND>::n) + ((OUT_KIND == MSQ_PLANE_U8X || OUT_KIND == MSQ_PLANE_SEL) ? 1 : 0);
+    static constexpr int n = (OUT_KIND == MSQ_PLANE_U6) ? 2 :     // U6: the high-nibble slot (16 B per lane) and the low-pair slot (8 B)
+        (IN_KIND != MSQ_PLANE_NONE ? 1 : 0) + (((MSQ_ABL & 256) && IsUnified<OUT_KIND>::v) ? 1 : HalfSlots<OUT_KIND>::n) + ((OUT_KIND == MSQ_PLANE_U8X || OUT_KIND == MSQ_PLANE_SEL) ? 1 : 0);
 };
 
 template <int IN_KIND, int OUT_KIND>
@@ -186,6 +195,7 @@ struct HalfRegs {
     u32x4_t inl;
     u32x4_t out[HalfSlots<OUT_KIND>::n ? HalfSlots<OUT_KIND>::n : 1];
     uint32_t ext;        // U8X: extension bits of this half; SEL: its select bits
+    u32x2_t lo;          // U6: the low-pair dwords of this half (inl = its high-nibble slot)
 };
 
 // --- packed-plane loads through buffer descriptors: the per-lane offset (lane * 16) never changes and the
@@ -218,6 +228,11 @@ MSQ_D int sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
 template <int IN_KIND, int OUT_KIND>
 MSQ_D void load_half_buf(HalfRegs<IN_KIND, OUT_KIND>& h, const PlaneRsrc& r, int lane16, uint32_t tile2kf) {
     constexpr int HS = HalfSlots<OUT_KIND>::n;
+    if (OUT_KIND == MSQ_PLANE_U6) {    // high-nibble slot: 64 lanes x 16 B per half (inlier descriptor); low-pair slot: 64 lanes x 8 B (out descriptor)
+        h.inl = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(r.inl, lane16, uni(tile2kf * 1024u), 0));
+        h.lo = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(r.out, lane16 >> 1, uni(tile2kf * 512u), 0));
+        return;
+    }
     if (IN_KIND != MSQ_PLANE_NONE)
         h.inl = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(r.inl, lane16, uni(tile2kf * 1024u), 0));
 #pragma unroll
@@ -237,7 +252,7 @@ MSQ_D void convert_quarter(u32x4_t (&wf)[4], const HalfRegs<IN_KIND, OUT_KIND>& 
     const int nf = q >> 1, hh = q & 1;
     if (IsUnified<OUT_KIND>::v) {      // scl[kf] byte nf; one convert per dword (+ rotate / and-or for the extension bit)
         const float s = scale_operand(scl[kf], nf);
-        const uint32_t o = h.out[nf >> 1][(nf & 1) * 2 + hh];
+        const uint32_t o = (OUT_KIND == MSQ_PLANE_U6) ? u6_code(h.inl[nf], h.lo[nf >> 1], 2 * nf + hh) : h.out[nf >> 1][(nf & 1) * 2 + hh];
         uint32_t r0 = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(o, s, false));
         uint32_t r1 = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(o, s, true));
         if (OUT_KIND == MSQ_PLANE_U8X) { r0 = ext_or(r0, h.ext, nf, 2 * hh); r1 = ext_or(r1, h.ext, nf, 2 * hh + 1); }
@@ -284,7 +299,8 @@ MSQ_D void keep_live4(u32x4_t& v) { asm volatile("" : "+v"(v)); }
 MSQ_D void keep_live1(uint32_t& v) { asm volatile("" : "+v"(v)); }
 template <int IN_KIND, int OUT_KIND>
 MSQ_D void keep_live(HalfRegs<IN_KIND, OUT_KIND>& h) {
-    if (IN_KIND != MSQ_PLANE_NONE) keep_live4(h.inl);
+    if (IN_KIND != MSQ_PLANE_NONE || OUT_KIND == MSQ_PLANE_U6) keep_live4(h.inl);
+    if (OUT_KIND == MSQ_PLANE_U6) asm volatile("" : "+v"(h.lo));
     if (OUT_KIND == MSQ_PLANE_U8X || OUT_KIND == MSQ_PLANE_SEL) keep_live1(h.ext);
 #pragma unroll
     for (int s = 0; s < HalfSlots<OUT_KIND>::n; ++s) keep_live4(h.out[s]);

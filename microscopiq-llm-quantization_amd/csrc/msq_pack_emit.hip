@@ -278,7 +278,7 @@ extern "C" int msq_pack_fused_(const float* W, void* inl_plane, void* out_plane,
         if (block == 16) { if (hw == 1) MSQ_PT(16, MSQ_PLANE_FP4, MSQ_PLANE_SEL, 1); else MSQ_PT(16, MSQ_PLANE_FP4, MSQ_PLANE_SEL, 0); }
         else { if (hw == 1) MSQ_PT(32, MSQ_PLANE_FP4, MSQ_PLANE_SEL, 1); else MSQ_PT(32, MSQ_PLANE_FP4, MSQ_PLANE_SEL, 0); }
     }
-    else if (in_kind == MSQ_PLANE_NONE && (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X))
+    else if (in_kind == MSQ_PLANE_NONE && (out_kind == MSQ_PLANE_U8 || out_kind == MSQ_PLANE_U8X || out_kind == MSQ_PLANE_U6))
         return msq_pack_unified_(W, inl_plane, out_plane, scale_plane, &A, N, K, block, out_kind, hw, stream);
     else return MSQ_ERR_UNSUPPORTED;
 #undef MSQ_PTB

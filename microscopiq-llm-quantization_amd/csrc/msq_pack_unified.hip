@@ -14,6 +14,7 @@ extern "C" void msq_set_error_(const char* msg);
 // ===========================================================================
 // Fused pack, unified layout (MSQ-U1): as k_pack_tile, but every 32-k half row gets ONE scale and every
 // weight one e4m3 code (+ one extension bit when EXT: the 4th fraction bit of posit<8,1> outliers).
+// (MSQ-U6: the same with the top six bits of every code, see HWU below.)
 //   scale s = floor(log2(max|v|)) - 8 (+1 when max|v| 2^-s > 448): when an e4m3 outlier holds the maximum
 //   this is the outlier's own scale, so its codes are unchanged; inlier e2m1 values widen exactly.
 // Every code is decoded back with the GEMM's own instruction and compared with the fake-quant value.
@@ -24,7 +25,10 @@ extern "C" void msq_set_error_(const char* msg);
 // the two halves of a tile are independent work items) whenever the quantiser block fits (BS <= 32 or values only), else
 // the whole 64 x 64 tile.  The half tile needs 9.2 KB of LDS per wave instead of 17.4: four workgroups per CU instead of
 // two -- the kernel is latency-bound (one row per lane, LDS round trips between its phases), occupancy is what it lacks.
-template <int BS, bool EXT, int HW>
+// HWU = quantiser codec mode (0 / 1 / 2, see msq_pack_fused_) + 4 for the six-bit emit (MSQ-U6, include/msq.h; never with EXT): the same scale
+// rule and convert, then every code must have its two low bits clear and come back through u6_code -- the GEMMs' own decode -- and the
+// row leaves its four high-nibble dwords and its share of the low-pair dwords instead of the eight code dwords.
+template <int BS, bool EXT, int HWU>
 #ifndef MSQ_PACKU_MINB
 #define MSQ_PACKU_MINB 4
 #endif
@@ -35,6 +39,9 @@ k_pack_tile_u(const float* __restrict__ W, uint8_t* __restrict__ ext_plane, uint
     // a time, so that no 64-element register array is needed: the fake-quant values overwrite the inputs; the codes of
     // half h then go to bytes 32 h .. 32 h + 31 of the row (already consumed), the scale bytes to word KW and the
     // extension bytes to words KW + 1 .. once the halves are encoded.
+    constexpr int HW = HWU & 3;
+    constexpr bool U6 = (HWU & 4) != 0;
+    static_assert(!(U6 && EXT), "MSQ-U6 has no extension plane");
     constexpr int KW = (BS <= 32) ? 32 : 64;                     // k columns per wave
     constexpr int NH = KW / 32;                                  // 32-k halves per wave
     constexpr int ROW_W = KW + 4;                                // words per row
@@ -131,6 +138,30 @@ k_pack_tile_u(const float* __restrict__ W, uint8_t* __restrict__ ext_plane, uint
             if (EXT) d |= (((eb >> (2 * p)) & 1u) << 3) | (((eb >> (2 * p + 1)) & 1u) << 19);
             ok = ok && (d == expect);
         }
+        if constexpr (U6) {
+            // code dword j of this row (elements 4 j ..) is code dword i = 2 nf + (j & 1) of lane (c, g = j >> 1) of the tile, nf = row >> 4:
+            // build what the row contributes to that lane's slots, decode it back with u6_code and convert as the GEMM will
+            const int i0 = 2 * ((lane >> 4) & 1);                // i & 3 of the row's even code dwords
+            uint32_t hw6[4], lw6[4];
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const uint32_t hi = u6_hi(cw[2 * gq], cw[2 * gq + 1]);
+                const uint32_t lo = u6_lo(cw[2 * gq], i0) | u6_lo(cw[2 * gq + 1], i0 + 1);
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int j = 2 * gq + q;
+                    const uint32_t cd = u6_code(hi, lo, i0 + q);
+                    const uint32_t d0 = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(cd, s_op, false));
+                    const uint32_t d1 = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(cd, s_op, true));
+                    ok = ok && ((cw[j] & 0x03030303u) == 0u);
+                    ok = ok && (d0 == ((f2u(v[4 * j]) >> 16) | (f2u(v[4 * j + 1]) & 0xFFFF0000u)));
+                    ok = ok && (d1 == ((f2u(v[4 * j + 2]) >> 16) | (f2u(v[4 * j + 3]) & 0xFFFF0000u)));
+                }
+                hw6[gq] = hi; lw6[gq] = lo;
+            }
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) { cw[gq] = hw6[gq]; cw[4 + gq] = lw6[gq]; }   // the row's words: 0..3 high nibbles of k-group g, 4..7 its low-pair share
+        }
         if (!ok && !bad) status |= MSQ_STATUS_INEXACT;
         uint32_t* crow = reinterpret_cast<uint32_t*>(myrow) + h * 8;     // bytes 32 h ..
 #pragma unroll
@@ -154,6 +185,20 @@ k_pack_tile_u(const float* __restrict__ W, uint8_t* __restrict__ ext_plane, uint
         const int kf = kf0 + h;
         uint32_t ew = 0;
         sc[h] = 0;
+        if constexpr (U6) {
+            uint32_t hi4[4], lo2[2] = {0u, 0u};
+#pragma unroll
+            for (int nf = 0; nf < 4; ++nf) {
+                const uint32_t* r = rows + (nf * 16 + c) * ROW_W;
+                sc[h] |= ((r[KW] >> (8 * h)) & 0xFFu) << (8 * nf);
+                hi4[nf] = r[h * 8 + g];
+                lo2[nf >> 1] |= r[h * 8 + 4 + g];
+            }
+            *reinterpret_cast<uint4*>(ext_plane + ((tile * 2 + kf) * 64 + lane) * 16) = make_uint4(hi4[0], hi4[1], hi4[2], hi4[3]);
+            *reinterpret_cast<uint2*>(code_plane + ((tile * 2 + kf) * 64 + lane) * 8) = make_uint2(lo2[0], lo2[1]);
+            if (g == 0) *reinterpret_cast<uint32_t*>(scl_plane + (tile * 16 + c) * 8 + kf * 4) = sc[h];
+            continue;
+        }
 #pragma unroll
         for (int nf = 0; nf < 4; ++nf) {
             const int n = nf * 16 + c, k8 = h * 4 + g;
@@ -186,6 +231,7 @@ extern "C" int msq_pack_unified_(const float* W, void* ext_plane, void* code_pla
 #define MSQ_PUB(EXTV, HWV) do { switch (block) { case 8: MSQ_PU(8, EXTV, HWV); break; case 16: MSQ_PU(16, EXTV, HWV); break; \
                                                  case 32: MSQ_PU(32, EXTV, HWV); break; default: MSQ_PU(64, EXTV, HWV); break; } } while (0)
     if (out_kind == MSQ_PLANE_U8) { if (hw == 1) MSQ_PUB(false, 1); else MSQ_PUB(false, 0); }
+    else if (out_kind == MSQ_PLANE_U6) { if (hw == 1) MSQ_PUB(false, 5); else MSQ_PUB(false, 4); }     // + 4: the six-bit emit
     else { if (hw == 2) MSQ_PUB(true, 2); else MSQ_PUB(true, 0); }
 #undef MSQ_PUB
 #undef MSQ_PU
@@ -194,7 +240,7 @@ extern "C" int msq_pack_unified_(const float* W, void* ext_plane, void* code_pla
     return MSQ_OK;
 }
 
-// values -> unified planes (no quantiser): out_kind MSQ_PLANE_U8 or MSQ_PLANE_U8X
+// values -> unified planes (no quantiser): out_kind MSQ_PLANE_U8, MSQ_PLANE_U8X or MSQ_PLANE_U6 (ext_plane = its high-nibble plane)
 extern "C" int msq_pack_values_u_(const float* W, void* ext_plane, void* code_plane, void* scale_plane, int* status,
                                   int64_t N, int64_t K, int out_kind, void* stream) {
     OutlierArgs A = {};
@@ -203,6 +249,7 @@ extern "C" int msq_pack_values_u_(const float* W, void* ext_plane, void* code_pl
     const dim3 grid((unsigned)((tiles + 3) / 4)), blk(256);
     hipStream_t st = (hipStream_t)stream;
     if (out_kind == MSQ_PLANE_U8) hipLaunchKernelGGL((k_pack_tile_u<0, false, 0>), grid, blk, 0, st, W, (uint8_t*)ext_plane, (uint8_t*)code_plane, (uint8_t*)scale_plane, A, N, K);
+    else if (out_kind == MSQ_PLANE_U6) hipLaunchKernelGGL((k_pack_tile_u<0, false, 4>), grid, blk, 0, st, W, (uint8_t*)ext_plane, (uint8_t*)code_plane, (uint8_t*)scale_plane, A, N, K);
     else hipLaunchKernelGGL((k_pack_tile_u<0, true, 0>), grid, blk, 0, st, W, (uint8_t*)ext_plane, (uint8_t*)code_plane, (uint8_t*)scale_plane, A, N, K);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { msq_set_error_(hipGetErrorString(e)); return MSQ_ERR_LAUNCH; }

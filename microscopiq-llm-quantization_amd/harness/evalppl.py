@@ -47,13 +47,17 @@ LLAMA_FUSE = [("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj")]      # s
 
 
 @torch.no_grad()
-def pack_layers(layers, path="bf16", fuse=None):
+def pack_layers(layers, path="bf16", fuse=None, kinds=None):
     """After quantize_layers_nearest / the GPTQ pass: swap every (already fake-quantised) Linear inside the decoder
     layers for a packed QuantLinear (what ``opt_pack3`` / ``make_quant3`` were meant to do, llm/opt.py:255-264).
     The weights are stored in the smallest exact single-plane kind (8.25 bits/weight for the harness default
     int2 / fp4 configuration) and the forward runs the fused dequant-GEMM.  EVERY nn.Linear that find_layers returns is
     packed (utils/modelutils.py:8-15): shapes off the kernels' tile grid are zero-padded at pack time (qlinear._pad2d).
     Returns (packed, kept_dense); kept_dense counts only Linears that are not on the GPU.
+
+    ``kinds`` (bf16 path): the single-plane kinds qlinear.pack_values tries, in order, for every layer; None = its default.
+    ``(PLANE_U6, PLANE_U8, PLANE_U8X, PLANE_BF16)`` stores the harness default int2 / fp4 configuration (``axes=[0]``) and
+    GPTQ outputs in the six-bit unified layout MSQ-U6 (6.25 bits/weight); a layer that does not fit it falls to the next kind.
 
     ``fuse`` (e.g. LLAMA_FUSE): groups of sibling Linears that read the same input are packed as one weight
     (qlinear.fuse_projections): one GEMM launch per group, the same values.
@@ -101,7 +105,7 @@ def pack_layers(layers, path="bf16", fuse=None):
                     continue
                 set_child(layer, name, m)
                 del names[name]
-        make_quant(layer, names, fuse=fuse)
+        make_quant(layer, names, fuse=fuse, kinds=kinds)
     return packed, dense
 
 

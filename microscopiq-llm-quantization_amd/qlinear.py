@@ -63,15 +63,16 @@ class PackedWeight:
         return 8.0 * self.nbytes / (self.n * self.k)
 
 
-LAYOUT_PLANES, LAYOUT_UNIFIED, LAYOUT_COMPACT = 0, 1, 2
-_LAYOUTS = {"planes": LAYOUT_PLANES, "unified": LAYOUT_UNIFIED, "compact": LAYOUT_COMPACT, LAYOUT_PLANES: LAYOUT_PLANES,
-            LAYOUT_UNIFIED: LAYOUT_UNIFIED, LAYOUT_COMPACT: LAYOUT_COMPACT}
+LAYOUT_PLANES, LAYOUT_UNIFIED, LAYOUT_COMPACT, LAYOUT_UNIFIED6 = 0, 1, 2, 3
+_LAYOUTS = {"planes": LAYOUT_PLANES, "unified": LAYOUT_UNIFIED, "compact": LAYOUT_COMPACT, "unified6": LAYOUT_UNIFIED6,
+            LAYOUT_PLANES: LAYOUT_PLANES, LAYOUT_UNIFIED: LAYOUT_UNIFIED, LAYOUT_COMPACT: LAYOUT_COMPACT, LAYOUT_UNIFIED6: LAYOUT_UNIFIED6}
 
 
 def packed_kinds(inlier_elem_format, outlier_elem_format, layout="planes"):
     """Plane kinds of a packed layout: "planes" = MSQ-T1 (inlier plane + outlier plane, two scales per
     block), "unified" = MSQ-U1 (one e4m3 code per weight [+ extension bit], one scale per 32 k), "compact" = MSQ-C1
-    (one e2m1 nibble + one select bit per weight, two scales per block: int2 / fp4 inliers with int2 / fp4 outliers)."""
+    (one e2m1 nibble + one select bit per weight, two scales per block: int2 / fp4 inliers with int2 / fp4 outliers),
+    "unified6" = MSQ-U6 (the top six bits of the MSQ-U1 code, one scale per 32 k: int2 / fp4 inliers and outliers)."""
     ik, ok = C.c_int(), C.c_int()
     check(lib().msq_packed_kinds_layout(format_id(inlier_elem_format), format_id(outlier_elem_format),
                                         _LAYOUTS[layout], C.byref(ik), C.byref(ok)), "msq_packed_kinds_layout")
@@ -94,7 +95,9 @@ def pack_weight(W, inlier_scale_bits=8, outlier_scale_bits=8, inlier_elem_format
     layout: "planes" (MSQ-T1), "unified" (MSQ-U1, smaller and faster; raises MsqError if a 32-k group
     cannot be represented exactly), "auto" (unified when the formats allow it and every group is
     exact, otherwise planes) or "compact" (MSQ-C1, opt-in: int2 / fp4 inliers with int2 / fp4 outliers at block 16 or 32
-    in 6.0 / 5.5 bits per weight; float32 compute only; raises MsqError for other formats / blocks or an inexact block).
+    in 6.0 / 5.5 bits per weight; float32 compute only; raises MsqError for other formats / blocks or an inexact block)
+    or "unified6" (MSQ-U6, opt-in: int2 / fp4 inliers and outliers in 6.25 bits per weight; float32 compute through the fused
+    launch, a half weight quantised in its dtype through pack_values; raises MsqError for other formats or values that do not fit).
 
     ``compute_dtype`` as quant.outlier_fakequant: an fp16 / bf16 weight is by default quantised IN its dtype (what the
     reference's RTN harness does with a half checkpoint, llm/llama.py:238), so that the packed layer holds exactly the
@@ -141,6 +144,16 @@ def pack_weight(W, inlier_scale_bits=8, outlier_scale_bits=8, inlier_elem_format
                 raise MsqError("pack_weight(layout='planes'): the %s weight's in-dtype fake-quant values fit neither the MSQ-T1 planes nor "
                                "the unified planes exactly; use layout='auto' (falls back to a 16-bit plane of those values) or "
                                "compute_dtype='float32'" % str(W.dtype).replace("torch.", ""))
+        if layout == "unified6":
+            try:                                                               # formats the layout does not hold: refused as on the float32 path
+                packed_kinds(inlier_elem_format, outlier_elem_format, layout)
+            except MsqError as e:
+                raise MsqError("pack_weight(layout='unified6'): %s" % e)
+            try:
+                return pack_values(Wq, (PLANE_U6,))
+            except MsqError:
+                raise MsqError("pack_weight(layout='unified6'): the %s weight's in-dtype fake-quant values do not fit the six-bit unified "
+                               "planes exactly" % str(W.dtype).replace("torch.", ""))
         kinds = {"unified": (PLANE_U8, PLANE_U8X), "auto": (PLANE_U8, PLANE_U8X, PLANE_BF16)}[layout]
         return pack_values(Wq, kinds)
     Wf = _pad2d(W.detach().contiguous().float(), N_MULT, K_MULT)
@@ -163,8 +176,8 @@ def _pack(Wf, inlier_scale_bits, outlier_scale_bits, inlier_elem_format, outlier
         ik, ok = packed_kinds(inlier_elem_format, outlier_elem_format, layout)
         ib, ob, sb, wb = packed_sizes(N, K, block_size, ik, ok)
     except MsqError as e:
-        if layout == "compact":
-            raise MsqError("pack_weight(layout='compact'): %s" % e)
+        if layout in ("compact", "unified6"):
+            raise MsqError("pack_weight(layout='%s'): %s" % (layout, e))
         raise
     dev = Wf.device
     inl = torch.empty(ib, dtype=torch.uint8, device=dev) if ib else None
@@ -172,12 +185,17 @@ def _pack(Wf, inlier_scale_bits, outlier_scale_bits, inlier_elem_format, outlier
     scl = torch.empty(sb, dtype=torch.uint8, device=dev) if sb else None
     ws = torch.empty(wb, dtype=torch.uint8, device=dev) if wb else None
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    check(lib().msq_outlier_pack(ptr(Wf), ptr(inl), ptr(out), ptr(scl), ptr(status), ptr(ws), wb, N, K, block_size,
-                                 format_id(inlier_elem_format), format_id(outlier_elem_format),
-                                 int(inlier_scale_bits), int(outlier_scale_bits), float(std_dev),
-                                 int(RoundingMode[round]), int(bool(flush_fp32_subnorms)), int(variant),
-                                 _LAYOUTS[layout], current_stream(dev)),
-          "msq_outlier_pack")
+    try:
+        check(lib().msq_outlier_pack(ptr(Wf), ptr(inl), ptr(out), ptr(scl), ptr(status), ptr(ws), wb, N, K, block_size,
+                                     format_id(inlier_elem_format), format_id(outlier_elem_format),
+                                     int(inlier_scale_bits), int(outlier_scale_bits), float(std_dev),
+                                     int(RoundingMode[round]), int(bool(flush_fp32_subnorms)), int(variant),
+                                     _LAYOUTS[layout], current_stream(dev)),
+              "msq_outlier_pack")
+    except MsqError as e:
+        if layout == "unified6":
+            raise MsqError("pack_weight(layout='unified6'): %s" % e)
+        raise
     st = int(status.item())
     if st & 1:
         raise AssertionError("shared_exp contains NaN values (scale overflow) while packing")
@@ -187,19 +205,20 @@ def _pack(Wf, inlier_scale_bits, outlier_scale_bits, inlier_elem_format, outlier
     return PackedWeight(inl, out, scl, N, K, block_size, ik, ok, n, k)
 
 
-PLANE_NONE, PLANE_BF16, PLANE_U8, PLANE_U8X, PLANE_SEL = 0, 4, 5, 6, 7
+PLANE_NONE, PLANE_BF16, PLANE_U8, PLANE_U8X, PLANE_SEL, PLANE_U6 = 0, 4, 5, 6, 7, 8
 
 
 def _layout_of(out_kind):
     """layout name of a packed weight's outlier-plane kind"""
-    return {PLANE_U8: "unified", PLANE_U8X: "unified", PLANE_SEL: "compact"}.get(out_kind, "planes")
+    return {PLANE_U8: "unified", PLANE_U8X: "unified", PLANE_SEL: "compact", PLANE_U6: "unified6"}.get(out_kind, "planes")
 
 
 def pack_values(Wq, kinds=(PLANE_U8, PLANE_U8X, PLANE_BF16)):
     """Pack a dense [N, K] tensor that already holds fake-quant values -- blocks along out_features
     (the reference harness default, llm/llama.py:229-237), the GPTQ solver's output (llm/gptq.py:166),
     anything -- into the first single-plane kind of `kinds` that represents every value exactly:
-    unified e4m3 (8.25 bits/weight), unified + extension bit (9.25) or plain bf16 (16).  Nothing is rounded."""
+    unified e4m3 (8.25 bits/weight), unified + extension bit (9.25) or plain bf16 (16).  Nothing is rounded.
+    ``PLANE_U6`` (six-bit unified, 6.25 bits/weight: int2 / fp4 values) is opt-in: name it first in `kinds`."""
     if not Wq.is_cuda:
         raise MsqError("pack_values needs a CUDA/HIP tensor (no CPU fallback)")
     if Wq.ndim != 2:
@@ -708,10 +727,11 @@ class QuantLinear(nn.Module):
         return m
 
     @classmethod
-    def from_dense(cls, linear, out_dtype=torch.bfloat16):
+    def from_dense(cls, linear, out_dtype=torch.bfloat16, kinds=None):
         """Pack a Linear whose weight ALREADY holds fake-quant values (RTN with any `axes`, or the GPTQ
-        solver's output): the layer is stored in the smallest single-plane kind that is exact."""
-        P = pack_values(linear.weight.data)
+        solver's output): the layer is stored in the first single-plane kind of ``kinds`` that is exact (None = pack_values'
+        default; e.g. ``(PLANE_U6, PLANE_U8, PLANE_U8X, PLANE_BF16)`` for int2 / fp4 values in 6.25 bits per weight)."""
+        P = pack_values(linear.weight.data) if kinds is None else pack_values(linear.weight.data, kinds)
         m = cls.__new__(cls)
         nn.Module.__init__(m)
         m.in_features, m.out_features, m.block_size = linear.in_features, linear.out_features, 32
@@ -827,9 +847,10 @@ def _compute_kw(layout):
     return dict(compute_dtype="float32") if layout == "compact" else {}
 
 
-def fuse_projections(parent, names, quantizer=None, layout="auto", path="bf16"):
+def fuse_projections(parent, names, quantizer=None, layout="auto", path="bf16", kinds=None):
     """Replace the nn.Linear children ``names`` of ``parent`` (same in_features, same bias-ness) by ProjectionSlices of one
-    packed module.  ``quantizer`` None = the weights already hold fake-quant values (pack_values / from_values)."""
+    packed module.  ``quantizer`` None = the weights already hold fake-quant values (pack_values / from_values); ``kinds``:
+    the single-plane kinds pack_values tries for them (None = its default)."""
     lins = [getattr(parent, n) for n in names]
     if not all(isinstance(l, nn.Linear) for l in lins):
         raise MsqError("fuse_projections: %r are not all nn.Linear" % (names,))
@@ -845,14 +866,14 @@ def fuse_projections(parent, names, quantizer=None, layout="auto", path="bf16"):
         proj = MXLinearW4A8.from_values(W, cat.bias.data if cat.bias is not None else None, out_dtype=od) if quantizer is None \
             else MXLinearW4A8.from_linear(cat, out_dtype=od)
     else:
-        proj = QuantLinear.from_dense(cat) if quantizer is None else QuantLinear.from_linear(cat, quantizer, layout=layout, **_compute_kw(layout))
+        proj = QuantLinear.from_dense(cat, kinds=kinds) if quantizer is None else QuantLinear.from_linear(cat, quantizer, layout=layout, **_compute_kw(layout))
     fused = FusedProjections(proj, [l.out_features for l in lins])
     for i, n in enumerate(names):
         setattr(parent, n, ProjectionSlice(fused, i, owner=(i == 0)))
     return fused
 
 
-def make_quant(module, quantizers, name='', layout="auto", fuse=None):
+def make_quant(module, quantizers, name='', layout="auto", fuse=None, kinds=None):
     """Swap every nn.Linear whose qualified name is in `quantizers` (name -> MXQuantizer) for a
     packed QuantLinear (the make_quant3 contract of llm/opt.py:258-264).  A value of None means "the weight
     already holds fake-quant values" (RTN along any axis / GPTQ): it is packed as it is (from_dense).
@@ -860,7 +881,8 @@ def make_quant(module, quantizers, name='', layout="auto", fuse=None):
     ``fuse``: groups of sibling names, e.g. ``[("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj")]``: wherever a
     module has all the Linears of a group as children (all listed in `quantizers`, with equal quantiser settings and blocks
     along in_features, or all None) they are packed as ONE weight (fuse_projections): one GEMM launch instead of two or
-    three, the same values.  ``layout="compact"`` (MSQ-C1; int2 / fp4 formats, block 16 / 32) quantises in float32."""
+    three, the same values.  ``layout="compact"`` (MSQ-C1; int2 / fp4 formats, block 16 / 32) quantises in float32.
+    ``kinds``: the single-plane kinds tried for the layers whose quantiser is None (None = pack_values' default)."""
     children = dict(module.named_children())
     for group in (fuse or ()):
         if not all(g in children and isinstance(children[g], nn.Linear) for g in group):
@@ -881,7 +903,7 @@ def make_quant(module, quantizers, name='', layout="auto", fuse=None):
             if [a % 2 for a in axes] != [1] or any(getattr(q, k_) != getattr(q0, k_) for q in qs for k_ in keys):
                 continue
         try:
-            fuse_projections(module, list(group), q0, layout)
+            fuse_projections(module, list(group), q0, layout, kinds=kinds)
         except MsqError:
             continue
         children = dict(module.named_children())
@@ -890,11 +912,11 @@ def make_quant(module, quantizers, name='', layout="auto", fuse=None):
         full = name + '.' + attr if name != '' else attr
         if isinstance(child, nn.Linear) and full in quantizers:
             if quantizers[full] is None:
-                setattr(module, attr, QuantLinear.from_dense(child))
+                setattr(module, attr, QuantLinear.from_dense(child, kinds=kinds))
             else:
                 setattr(module, attr, QuantLinear.from_linear(child, quantizers[full], layout=layout, **_compute_kw(layout)))
         elif not isinstance(child, (ProjectionSlice, QuantLinear, MXLinearW4A8)):
-            make_quant(child, quantizers, full, layout, fuse)
+            make_quant(child, quantizers, full, layout, fuse, kinds)
     return module
 
 
@@ -951,7 +973,7 @@ class RowParallelQuantLinear(nn.Module):
         """Quantise and pack this rank's K slice of a dense Linear.  ``path="bf16"``: fused dequant-GEMM shard
         (QuantLinear); ``"mx"``: the fake-quant values as an exact e4m3 operand with MX-FP8 activations
         (MXLinearW4A8.from_values).  Blocks run along K, so every shard's masks and scales equal the unsharded ones.
-        ``layout`` (bf16 path): packed layout of the shard, e.g. "compact" (float32 compute); None = QuantLinear.from_linear's default."""
+        ``layout`` (bf16 path): packed layout of the shard, e.g. "compact" (float32 compute) or "unified6"; None = QuantLinear.from_linear's default."""
         k0, k1 = cls.shard_bounds(linear.in_features, world_size, rank, quantizer.block_size, 128 if path == "mx" else 64)
         has_bias = linear.bias is not None and rank == 0
         Wl = linear.weight.data[:, k0:k1].contiguous()
