@@ -346,6 +346,29 @@ int msq_qlinear_f16x(const void* X, const void* inl_plane, const void* out_plane
                      int in_kind, int out_kind, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Grouped fused dequant-GEMM (mixture of experts) -- NEW; the reference quantises the expert Linears w1 / w3 / w2 of a Mixtral one by one
+ * (llm/llama.py:37-40 through find_layers) and multiplies them in the Python expert loop of transformers.
+ *   For `rows` routed rows SORTED BY EXPERT:  Y[r, :] = X[row_index[r], :] . W_e(r)^T (+ bias[e(r), :]),  e(r) = the expert whose range
+ *   [row_offsets[e], row_offsets[e + 1]) holds r (csrc/msq_gemm_grouped.hip: k_qgemm_grouped).
+ *   X bf16 [x_rows, K]; row_index DEVICE int32 [rows] (NULL = identity: row r reads X[r]); row_offsets DEVICE int32 [E + 1], ascending,
+ *   [0] = 0; the planes of expert e are exactly what msq_pack_values / msq_outlier_pack write for one [N, K] weight, at base + e * stride
+ *   bytes (strides >= msq_packed_sizes, multiples of 4); kinds MSQ_PLANE_U8 / _U8X / _U6 with in_kind NONE, others MSQ_ERR_UNSUPPORTED;
+ *   N % 256 == 0, K % 64 == 0; bias f32 [E, N] or NULL; Y [rows, N], y_dtype 0 = f32, 1 = fp16, 2 = bf16.
+ *   `rows` is the CAPACITY (the host's upper bound, e.g. tokens * top_k): the launch geometry is a function of (rows, E, N) alone, the real
+ *   row count is row_offsets[E]; only rows below min(row_offsets[E], rows) are stored, each by the block of its own expert.  No host
+ *   knowledge of the per-expert counts, no workspace, no flags or atomics between blocks: capturable in a HIP graph, and an expert without
+ *   rows reads none of its bytes.
+ *   Every output element is an fp32 sum whose K order depends on its expert and 64-column strip only: a row's result is bit-identical
+ *   whether it is computed alone or among others, and from run to run.
+ *   msq_qlinear_grouped_plan: host arithmetic only, no device -- row_tile = rows per block (64), tile_slots = an upper bound of
+ *   sum_e ceil(m_e / row_tile) over every split of `rows` into E counts, blocks = (N / 64) * tile_slots. */
+int msq_qlinear_grouped_plan(int64_t rows, int E, int64_t N, int64_t K, int out_kind, int* row_tile, int* tile_slots, int64_t* blocks);
+int msq_qlinear_grouped_bf16(const void* X, int64_t x_rows, const int32_t* row_index, const int32_t* row_offsets,
+                             const void* inl_planes, const void* out_planes, const void* scale_planes,
+                             int64_t inl_stride, int64_t out_stride, int64_t scale_stride, const float* bias, void* Y, int y_dtype,
+                             int64_t rows, int E, int64_t N, int64_t K, int block, int in_kind, int out_kind, void* stream);
+
+/* ---------------------------------------------------------------------------
  * W4A8 Linear -- NEW; replaces the activation quantisation + F.linear of
  * number_system/mx/linear.py:66-73,91 (MXLinear with an 8-bit a_elem_format; BASELINE config 3).
  *   msq_act_quant_bf16: X [M,K] f32 -> MicroScopiQ outlier-aware MX fake-quant along K

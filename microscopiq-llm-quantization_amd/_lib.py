@@ -64,6 +64,9 @@ _SIGS = {
     "msq_qgemm256p_segments": (C.c_int, [_i32] * 6 + [C.POINTER(_i32), _i32]),
     "msq_qlinear_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
     "msq_qlinear_f16x": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "msq_qlinear_grouped_plan": (C.c_int, [_i64, _i32, _i64, _i64, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)]),
+    "msq_qlinear_grouped_bf16": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i64, _i32, _i64, _i64,
+                                           _i32, _i32, _i32, _vp]),
     "msq_act_quant_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "msq_act_quant_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32,
                                      _i32, _i32, _vp]),

@@ -72,6 +72,11 @@ def _has_unified6(layers):
 def save_packed(model, path, shard=0, world_size=1):
     """Write every tensor of `model` (packed planes included) and the layer table to `path`."""
     from safetensors.torch import save_file
+    from .moe import QuantExperts
+    for name, m in model.named_modules():
+        if isinstance(m, QuantExperts):
+            raise MsqError("save_packed: module %r holds packed experts (moe.QuantExperts); this checkpoint format describes packed Linears "
+                           "only and does not record expert stacks yet" % name)
     layers = {}
     fused = _fused_groups(model)
     for name, m in _packed_layers(model).items():

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from ..quant import MXQuantizer, quantize_mx_outlier_v1
-from .modelutils import find_layers
+from .modelutils import find_experts, find_layers
 
 # llm/llama.py:229-237, llm/opt.py:193-201: the harness hard-codes this configuration
 DEFAULT_QUANT = dict(inlier_scale_bits=8, outlier_scale_bits=8, inlier_elem_format='int2',
@@ -26,19 +26,32 @@ def quantize_layers_nearest(layers, dev, quant_cfg=None, log=None):
     cfg = dict(DEFAULT_QUANT)
     if quant_cfg:
         cfg.update(quant_cfg)
+    def rtn(W, dtype):
+        quantizer = MXQuantizer()
+        quantizer.configure(**cfg)
+        quantizer.find_params(W, weight=True)
+        return quantize_mx_outlier_v1(
+            W, quantizer.inlier_scale_bits, quantizer.outlier_scale_bits, quantizer.inlier_elem_format,
+            quantizer.outlier_elem_format, quantizer.shared_exp_method, quantizer.std_dev, quantizer.axes,
+            quantizer.block_size, quantizer.round, quantizer.flush_fp32_subnorms, quantizer.custom_cuda
+        ).to(dtype)
+
     for i, layer in enumerate(layers):
         layer.to(dev)
+        dtype = next(iter(layer.parameters())).dtype
         subset = find_layers(layer)
         for name in subset:
-            quantizer = MXQuantizer()
-            quantizer.configure(**cfg)
-            W = subset[name].weight.data
-            quantizer.find_params(W, weight=True)
-            subset[name].weight.data = quantize_mx_outlier_v1(
-                W, quantizer.inlier_scale_bits, quantizer.outlier_scale_bits, quantizer.inlier_elem_format,
-                quantizer.outlier_elem_format, quantizer.shared_exp_method, quantizer.std_dev, quantizer.axes,
-                quantizer.block_size, quantizer.round, quantizer.flush_fp32_subnorms, quantizer.custom_cuda
-            ).to(next(iter(layer.parameters())).dtype)
+            subset[name].weight.data = rtn(subset[name].weight.data, dtype)
+        # stacked experts (3-D gate_up_proj / down_proj): every expert's gate half, up half and down weight is quantised as its own 2-D
+        # weight -- what the loop above did when they were the Linears w1 / w3 / w2 (llm/llama.py:226-253).  Halves separately: blocks along
+        # out_features must not straddle gate and up.  The router weight is left alone.
+        for mod in find_experts(layer).values():
+            gu, dn = mod.gate_up_proj.data, mod.down_proj.data
+            inter = gu.shape[1] // 2
+            for e in range(gu.shape[0]):
+                gu[e, :inter] = rtn(gu[e, :inter].contiguous(), dtype)
+                gu[e, inter:] = rtn(gu[e, inter:].contiguous(), dtype)
+                dn[e] = rtn(dn[e].contiguous(), dtype)
         if log:
             log(i)
 
@@ -53,7 +66,9 @@ def pack_layers(layers, path="bf16", fuse=None, kinds=None):
     The weights are stored in the smallest exact single-plane kind (8.25 bits/weight for the harness default
     int2 / fp4 configuration) and the forward runs the fused dequant-GEMM.  EVERY nn.Linear that find_layers returns is
     packed (utils/modelutils.py:8-15): shapes off the kernels' tile grid are zero-padded at pack time (qlinear._pad2d).
-    Returns (packed, kept_dense); kept_dense counts only Linears that are not on the GPU.
+    Returns (packed, kept_dense); kept_dense counts only Linears that are not on the GPU.  Stacked-experts modules (find_experts:
+    a Mixtral's experts) on the GPU are swapped for moe.QuantExperts as well (pack_expert_modules; bf16 path only, ``path="mx"``
+    leaves them as they are); they are not counted in the returned pair.
 
     ``kinds`` (bf16 path): the single-plane kinds qlinear.pack_values tries, in order, for every layer; None = its default.
     ``(PLANE_U6, PLANE_U8, PLANE_U8X, PLANE_BF16)`` stores the harness default int2 / fp4 configuration (``axes=[0]``) and
@@ -106,7 +121,17 @@ def pack_layers(layers, path="bf16", fuse=None, kinds=None):
                 set_child(layer, name, m)
                 del names[name]
         make_quant(layer, names, fuse=fuse, kinds=kinds)
+        if path != "mx":
+            pack_expert_modules(layer, kinds=kinds)
     return packed, dense
+
+
+@torch.no_grad()
+def pack_expert_modules(layers, kinds=None):
+    """Swap every (already fake-quantised) stacked-experts module on the GPU inside `layers` for a packed moe.QuantExperts
+    (``kinds`` as pack_layers; None = MSQ-U1 with or without the extension bit).  Returns the number of modules swapped."""
+    from ..moe import pack_expert_modules as _pack
+    return _pack(layers, kinds=kinds)
 
 
 @torch.no_grad()

@@ -18,3 +18,16 @@ def find_layers(module, layers=(nn.Conv2d, nn.Linear), name=''):
             hits[(name + '.' + path if name and path else name or path)] = sub
             closed.append(path)
     return hits
+
+
+def find_experts(module, name=''):
+    """{qualified name: module} for every sub-module that keeps its experts as stacked 3-D parameters ``gate_up_proj``
+    [E, 2I, H] and ``down_proj`` [E, H, I] (current transformers' Mixtral: the `w1` / `w3` / `w2` Linears that
+    utils/modelutils.py:8-15 found in the reference's transformers generation no longer exist).  Duck-typed: no
+    transformers class is named."""
+    hits = {}
+    for path, sub in module.named_modules():
+        gu, dn = getattr(sub, 'gate_up_proj', None), getattr(sub, 'down_proj', None)
+        if isinstance(gu, nn.Parameter) and isinstance(dn, nn.Parameter) and gu.ndim == 3 and dn.ndim == 3:
+            hits[(name + '.' + path if name and path else name or path)] = sub
+    return hits

@@ -18,7 +18,7 @@ import torch.nn as nn
 from ..quant import MXQuantizer, Quantizer
 from .evalppl import DEFAULT_QUANT
 from .gptq import GPTQ
-from .modelutils import find_layers
+from .modelutils import find_experts, find_layers
 
 LLAMA_TRUE_SEQUENTIAL = [['self_attn.k_proj', 'self_attn.v_proj', 'self_attn.q_proj'], ['self_attn.o_proj'],
                          ['mlp.up_proj', 'mlp.gate_proj'], ['mlp.down_proj']]                     # llm/llama.py:116-121
@@ -81,6 +81,9 @@ def _sequential(model, layers, prefix, pre_modules, dataloader, dev, args, true_
     for i in range(len(layers)):
         layer = layers[i].to(dev)
         full = find_layers(layer)
+        if log and find_experts(layer):
+            log("%d: stacked experts (%s) are NOT calibrated or quantised by the GPTQ pass: only nn.Linear layers are"
+                % (i, ", ".join(find_experts(layer))))
         groups = [[nm for nm in g if nm in full] for g in true_sequential_groups] if (args.true_sequential and true_sequential_groups) else [list(full.keys())]
         run = lambda j: _first(layer(inps[j], *rest[j][0], **rest[j][1]))
         for names in groups:
