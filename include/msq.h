@@ -483,6 +483,46 @@ int msq_kv_group_quant(const void* in, void* out, int dtype, int64_t B, int64_t 
                        int quantize_bit, int64_t group_size, int along_tokens, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Packed MX KV cache -- NEW.  One attention layer's cache as plain OCP-MX codes + E8M0 scale bytes on KIVI's axes
+ * (the ones msq.kvcache.mx_quantize_keys / mx_quantize_values use) instead of fake-quantised half-precision tensors.  For B sequences,
+ * H kv heads, a token capacity S_cap (a multiple of 32) and head_dim D (a multiple of 32, at most 256):
+ *   K codes, V codes  [B, H, S_cap, D] bytes (MSQ_FMT_FP8_E4M3) or [B, H, S_cap, D / 2] bytes (MSQ_FMT_FP4_E2M1, even d in the low nibble)
+ *   K scales          [B, H, S_cap / 32, D] bytes   (blocks of 32 consecutive tokens of one channel)
+ *   V scales          [B, H, S_cap, D / 32] bytes   (blocks of 32 consecutive head_dim entries of one token)
+ * decode(code) * 2^(scale - 127) equals _quantize_mx(x.float(), 8, fmt, axes=[axis], block_size=32) (mx_ops.py:332-457, Python path,
+ * round to nearest) bit for bit; a half-precision input is read as the float32 values it holds.
+ *   msq_kv_mx_pack    in [B, H, T, D] contiguous (dtype 0 f32, 1 f16, 2 bf16) -> tokens pos .. pos + T of the planes.  T % 32 == 0,
+ *                     pos % 32 == 0, pos + T <= S_cap.  along_tokens = 1: the K form, 0: the V form.  status_flag receives MSQ_STATUS_NAN
+ *                     when a block holds Inf / NaN (as msq_mx_pack_a8).
+ *   msq_kv_mx_unpack  tokens pos .. pos + T of the planes -> out [B, H, T, D] contiguous, rounded once to `dtype`.
+ *   msq_kv_mx_attn_decode   out[b, hq, :] = softmax(scaling q[b, hq, :] K^T + bias[b, :]) V for ONE query token per sequence: the sum runs
+ *                     over the packed tokens 0 .. S_packed (S_packed % 32 == 0, <= S_cap) and then the tail_len tokens of k_tail / v_tail
+ *                     [B, Hkv, tail_cap, D] (tokens that do not fill a group yet, in the q dtype).  q [B, Hq, D] f16 (q_dtype 1) or bf16
+ *                     (2); Hq % Hkv == 0 with at most 8 query heads per kv head; D 64 or 128; bias [B, S_packed + tail_len] f32 or NULL,
+ *                     may hold -inf (a row whose every position is -inf gives zeros); out [B, Hq, D] in out_dtype = q_dtype or 0 (f32;
+ *                     the half output is the f32 output rounded).  S_packed + tail_len == 0 is an argument error.  Two launches: every
+ *                     (sequence, kv head, token split) writes its partial (acc[D], m, l) to the workspace, the second combines the splits
+ *                     in ascending order: no atomics, equal inputs give equal bits.
+ *   msq_kv_mx_attn_plan     the token splits (host arithmetic, no device): split s covers the packed tokens s * split_tokens ..
+ *                     min((s + 1) * split_tokens, S_packed), the last one also the tail; a function of S_packed alone, so a sequence gives
+ *                     the same bits whatever it is batched with.  Any output pointer may be NULL.
+ *   msq_kv_mx_attn_workspace_bytes   the plan's workspace size (B Hq n_splits (D + 2) floats), or a negative MSQ_ERR_*.
+ * Not built: lengths held on the device (and with them HIP-graph capture of a step), paged / block-table caches, prefill attention over
+ * the codes, MicroScopiQ outlier caches, more than one query token.
+ * ------------------------------------------------------------------------- */
+int msq_kv_mx_pack(const void* in, int dtype, void* codes, void* scales, int64_t B, int64_t H, int64_t T, int64_t D, int64_t S_cap,
+                   int64_t pos, int elem_fmt, int along_tokens, int* status_flag, void* stream);
+int msq_kv_mx_unpack(const void* codes, const void* scales, void* out, int dtype, int64_t B, int64_t H, int64_t D, int64_t S_cap,
+                     int64_t pos, int64_t T, int elem_fmt, int along_tokens, void* stream);
+int msq_kv_mx_attn_plan(int64_t B, int Hq, int Hkv, int D, int64_t S_packed, int64_t tail_len, int* n_splits, int* split_tokens,
+                        int64_t* workspace_bytes);
+int64_t msq_kv_mx_attn_workspace_bytes(int64_t B, int Hq, int Hkv, int D, int64_t S_packed, int64_t tail_len);
+int msq_kv_mx_attn_decode(const void* q, int q_dtype, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                          int64_t S_packed, int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_len, int64_t tail_cap,
+                          const float* bias, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt, float scaling,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Bfloat-rounded vector ops around the MX Linear.  The reference emulates every non-GEMM op as the
  * torch op followed by quantize_elemwise_op (number_system/mx/vector_ops.py); each entry below is that whole chain as
  * ONE launch with the rounding Q() = quantize_elemwise (bits, exp_bits, max_norm, rmode, saturate_normals = false,

@@ -1,0 +1,584 @@
+// msq_kv_packed.hip -- the PACKED MX KV cache: plain OCP-MX codes + E8M0 scale bytes instead of fake-quantised
+// half-precision tensors, and single-token decode attention that reads the codes.
+//
+// Planes of one attention layer (B sequences, H kv heads, S_cap tokens, head_dim D; KIVI's axes, the ones msq.kvcache.mx_quantize_keys /
+// mx_quantize_values use):
+//   K codes  [B, H, S_cap, D] bytes (e4m3) or [B, H, S_cap, D / 2] bytes (e2m1, even d in the low nibble)
+//   K scales [B, H, S_cap / 32, D] bytes      one block = 32 consecutive TOKENS of one channel
+//   V codes  as K codes
+//   V scales [B, H, S_cap, D / 32] bytes      one block = 32 consecutive head_dim entries of one token
+// decode(code) * 2^(scale - 127) == _quantize_mx(x.float(), 8, fmt, axes=[axis], block_size=32) bit for bit: the float32 Python-path
+// arithmetic of msq_mx.hip k_mx_pack (shared exponent floor(torch.log2(max)), round half away through the sticky bit, e4m3 clamped first).
+//
+// Attention: out = softmax(scaling q K^T + bias) V for ONE query token per sequence over the packed tokens 0 .. S_packed and then the
+// tail (tokens that do not fill a group yet, kept in the cache dtype).  A block owns one (sequence, kv head, token split) and serves every
+// query head of the group, so a code byte is read once per group; a lane owns 8 consecutive channels of one token (K and V of the same
+// token: one address pattern), D / 8 lanes share a token.  fp32 dot products, fp32 online softmax kept PER LANE over the tokens the lane
+// has seen (no cross-lane traffic in the loop beyond the dot product's butterfly), merged across the lanes of a wave by shuffles and
+// across the four waves through LDS in a fixed order; every split writes (acc[D], m, l) to the workspace and a second launch combines the
+// splits in ascending order.  No atomics, no flags, no block waits on another: equal inputs give equal bits.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/msq.h"
+#include "msq_device.h"
+#include "msq_mx_pack_core.h"
+
+using namespace msq;
+
+extern "C" void msq_set_error_(const char* msg);      // msq_quant.hip: the message msq_last_error() returns
+
+namespace {
+
+typedef float v2f_t __attribute__((ext_vector_type(2)));
+typedef short v2s_t __attribute__((ext_vector_type(2)));
+
+MSQ_D float half_lo(uint32_t w, int dt) { return dt == 1 ? (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu)) : u2f(w << 16); }
+MSQ_D float half_hi(uint32_t w, int dt) { return dt == 1 ? (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)) : u2f(w & 0xFFFF0000u); }
+template <int DT> MSQ_D float ld_any(const void* p, int64_t i) {
+    if (DT == 0) return reinterpret_cast<const float*>(p)[i];
+    const uint16_t h = reinterpret_cast<const uint16_t*>(p)[i];
+    return DT == 1 ? (float)__builtin_bit_cast(_Float16, h) : u2f((uint32_t)h << 16);
+}
+template <int DT> MSQ_D void st_pair(void* p, int64_t i, float v0, float v1) {      // i even
+    if (DT == 0) { *reinterpret_cast<float2*>(reinterpret_cast<float*>(p) + i) = make_float2(v0, v1); return; }
+    uint32_t w;
+    if (DT == 1) w = (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)v0) | ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)v1) << 16);
+    else w = (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)v0) | ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)v1) << 16);
+    *reinterpret_cast<uint32_t*>(reinterpret_cast<uint16_t*>(p) + i) = w;
+}
+
+// One MX block of 32 float32 values -> codes (e4m3: 8 words, element i in byte i; e2m1: 4 words, element i in nibble i) + the scale byte:
+// the arithmetic of msq_mx.hip k_mx_pack (activations / weights, flush_fp32_subnorms = 0) on a register array.
+template <bool FP4>
+MSQ_D void mx_block32(const float (&a)[32], uint32_t (&cw)[FP4 ? 4 : 8], int& sb, int& status) {
+    uint32_t mag = 0u;
+#pragma unroll
+    for (int b = 0; b < 32; ++b) { const uint32_t t = f2u(a[b]) & 0x7FFFFFFFu; mag = t > mag ? t : mag; }
+    sb = mx_scale_byte(biased_exp_py(mag), FP4 ? 2 : 8, status);
+    const float s_op = u2f((uint32_t)sb << 23);                  // the converts read the exponent field only
+    const float bound = __builtin_ldexpf(448.f, sb - 127);       // e4m3 max_norm x scale (exact)
+    const uint32_t qb = half_away_quirk_bits(sb - 127 - (FP4 ? 2 : 10));
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {
+        float x0 = sticky_half_away(a[2 * p], qb), x1 = sticky_half_away(a[2 * p + 1], qb);
+        if (FP4) {
+            uint32_t w = (p & 3) ? cw[p >> 2] : 0u;
+            if ((p & 3) == 0) w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, x0, x1, s_op, 0);
+            else if ((p & 3) == 1) w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, x0, x1, s_op, 1);
+            else if ((p & 3) == 2) w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, x0, x1, s_op, 2);
+            else w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, x0, x1, s_op, 3);
+            cw[p >> 2] = w;
+        } else {
+            x0 = __builtin_amdgcn_fmed3f(x0, -bound, bound); x1 = __builtin_amdgcn_fmed3f(x1, -bound, bound);   // e4m3 does not saturate
+            v2s_t cur = __builtin_bit_cast(v2s_t, (p & 1) ? cw[p >> 1] : 0u);
+            if ((p & 1) == 0) cur = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(cur, x0, x1, s_op, false);
+            else cur = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(cur, x0, x1, s_op, true);
+            cw[p >> 1] = __builtin_bit_cast(uint32_t, cur);
+        }
+    }
+}
+
+// ---- pack, K form: one lane per (b h, token group, channel), channel fastest: 32 strided reads, coalesced across the lanes
+template <int DT, bool FP4>
+__global__ void __launch_bounds__(256)
+k_kvp_pack_k(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t total, int64_t T, int D,
+             int64_t S_cap, int64_t pos, int* status_flag) {
+    const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = t0 < total;                                   // total is even and so is D: a nibble pair is live or dead as one
+    const int64_t t = live ? t0 : 0;
+    const int64_t ng = T / 32;
+    const int d = (int)(t % D);
+    const int64_t tg = (t / D) % ng, bh = t / ((int64_t)D * ng);
+    float a[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) a[i] = ld_any<DT>(in, (bh * T + tg * 32 + i) * D + d);
+    uint32_t cw[FP4 ? 4 : 8];
+    int sb, status = 0;
+    mx_block32<FP4>(a, cw, sb, status);
+    const int64_t row0 = bh * S_cap + pos + tg * 32;
+    if (FP4) {
+        uint32_t ow[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ow[j] = (uint32_t)__shfl_xor((int)cw[j & 3], 1, 64);     // the odd neighbour's nibbles
+        if (live && !(d & 1)) {
+#pragma unroll
+            for (int i = 0; i < 32; ++i) {
+                const uint32_t lo = (cw[(i >> 3) & 3] >> (4 * (i & 7))) & 0xFu, hi = (ow[i >> 3] >> (4 * (i & 7))) & 0xFu;
+                codes[(row0 + i) * (D / 2) + (d >> 1)] = (uint8_t)(lo | (hi << 4));
+            }
+        }
+    } else if (live) {
+#pragma unroll
+        for (int i = 0; i < 32; ++i) codes[(row0 + i) * D + d] = (uint8_t)((cw[(i >> 2) & (FP4 ? 3 : 7)] >> (8 * (i & 3))) & 0xFFu);
+    }
+    if (live) scales[(bh * (S_cap / 32) + pos / 32 + tg) * D + d] = (uint8_t)sb;
+    if (live && status && status_flag) atomicOr(status_flag, status);
+}
+
+// ---- pack, V form: one lane per (b h, token, block of 32 channels): 16-byte reads and stores
+template <int DT, bool FP4>
+__global__ void __launch_bounds__(256)
+k_kvp_pack_v(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t total, int64_t T, int D,
+             int64_t S_cap, int64_t pos, int* status_flag) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int nb = D / 32;
+    const int blk = (int)(t % nb);
+    const int64_t row = t / nb, bh = row / T, tok = row % T;
+    float a[32];
+    if (DT == 0) {
+        const float4* s4 = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(in) + row * D + blk * 32);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const float4 v = s4[k]; a[4 * k] = v.x; a[4 * k + 1] = v.y; a[4 * k + 2] = v.z; a[4 * k + 3] = v.w; }
+    } else {
+        const uint4* s8 = reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(in) + row * D + blk * 32);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint4 v = s8[k];
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { a[8 * k + 2 * j] = half_lo(w[j], DT); a[8 * k + 2 * j + 1] = half_hi(w[j], DT); }
+        }
+    }
+    uint32_t cw[FP4 ? 4 : 8];
+    int sb, status = 0;
+    mx_block32<FP4>(a, cw, sb, status);
+    const int64_t dst = bh * S_cap + pos + tok;
+    if (FP4) {
+        *reinterpret_cast<uint4*>(codes + dst * (D / 2) + blk * 16) = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+    } else {
+        uint4* o = reinterpret_cast<uint4*>(codes + dst * D + blk * 32);
+        o[0] = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+        o[1] = make_uint4(cw[FP4 ? 0 : 4], cw[FP4 ? 1 : 5], cw[FP4 ? 2 : 6], cw[FP4 ? 3 : 7]);
+    }
+    scales[dst * nb + blk] = (uint8_t)sb;
+    if (status && status_flag) atomicOr(status_flag, status);
+}
+
+// value of a code pair: the scaled convert at scale 1, then the exact power of two (scale byte 255: the block held Inf / NaN)
+MSQ_D float apply_e8m0(float v, int sb) { return sb == 255 ? u2f(0x7FC00000u) : __builtin_ldexpf(v, sb - 127); }
+
+// ---- unpack: one lane per (b h, token, channel pair)
+template <int DT, bool FP4>
+__global__ void __launch_bounds__(256)
+k_kvp_unpack(const uint8_t* __restrict__ codes, const uint8_t* __restrict__ scales, void* __restrict__ out, int64_t total, int64_t T, int D,
+             int64_t S_cap, int64_t pos, int along_tokens) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int hd = D / 2;
+    const int dp = (int)(t % hd);
+    const int64_t tok = (t / hd) % T, bh = t / ((int64_t)hd * T);
+    const int64_t src = bh * S_cap + pos + tok;
+    v2f_t v;
+    if (FP4) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4((uint32_t)codes[src * hd + dp], 1.0f, 0);
+    else v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8((uint32_t)*reinterpret_cast<const uint16_t*>(codes + src * D + 2 * dp), 1.0f, false);
+    int s0, s1;
+    if (along_tokens) {
+        const uint8_t* sp = scales + (bh * (S_cap / 32) + (pos + tok) / 32) * D + 2 * dp;
+        s0 = sp[0]; s1 = sp[1];
+    } else {
+        s0 = s1 = scales[src * (D / 32) + (2 * dp) / 32];
+    }
+    st_pair<DT>(out, (bh * T + tok) * D + 2 * dp, apply_e8m0(v[0], s0), apply_e8m0(v[1], s1));
+}
+
+// =====================================================================================================================
+// decode attention
+// =====================================================================================================================
+struct AttnArgs {
+    const void* q; const uint8_t* kc; const uint8_t* ks; const uint8_t* vc; const uint8_t* vs; const void* kt; const void* vt;
+    const float* bias; float* ws;
+    int Hq, G, nsplit, gps, S_packed, tail_len, tail_cap;
+    int64_t S_cap;
+    float scaling;
+};
+
+constexpr float LOG2E = 1.44269504088896340736f;
+MSQ_D float ex(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }                 // e^x; e^-inf = 0
+MSQ_D float e8m0_f32(uint32_t sb) { return sb ? u2f(sb << 23) : u2f(0x00400000u); }   // 2^(sb - 127)
+MSQ_D float neg_inf() { return -__builtin_inff(); }
+
+// one group of NP tokens per lane: the scores sc[p][g] are in hand; fold them into the lane's running (m, l), rescale acc once, and leave the
+// probabilities in sc
+template <int NP, int GMAX>
+MSQ_D void softmax_fold(float (&sc)[NP][GMAX], float (&m)[GMAX], float (&l)[GMAX], float (&acc)[GMAX][8]) {
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g) {
+        float mn = m[g];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) mn = __builtin_fmaxf(mn, sc[p][g]);
+        const float mm = (mn == neg_inf()) ? 0.f : mn;              // everything masked so far: e^(-inf - 0) = 0, never inf - inf
+        const float a = ex(m[g] - mm);
+        float ls = l[g] * a;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[g][j] *= a;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) { sc[p][g] = ex(sc[p][g] - mm); ls += sc[p][g]; }
+        l[g] = ls; m[g] = mn;
+    }
+}
+
+template <int D, bool FP4, int GMAX, int QDT>
+__global__ void __launch_bounds__(256)
+k_kvp_attn_split(const AttnArgs A) {
+    constexpr int LPT = D / 8, TP = 64 / LPT, NP = 32 / TP;          // lanes per token, tokens per pass of a wave, passes per group of 32
+    constexpr int CB = FP4 ? 4 : 8;                                   // code bytes of a lane's 8 channels
+    __shared__ float red[4][GMAX][D + 2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c = lane % LPT, ts = lane / LPT;
+    const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+    const int G = A.G, Hkv = A.Hq / G;
+    const int64_t bh = (int64_t)b * Hkv + hk;
+    const int stot = A.S_packed + A.tail_len;
+
+    float q[GMAX][8];
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g) {
+        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+        if (g < G) raw = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(A.q) + ((int64_t)b * A.Hq + hk * G + g) * D + c * 8);
+        const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { q[g][2 * j] = half_lo(w[j], QDT); q[g][2 * j + 1] = half_hi(w[j], QDT); }
+    }
+    float m[GMAX], l[GMAX], acc[GMAX][8];
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g) {
+        m[g] = neg_inf(); l[g] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[g][j] = 0.f;
+    }
+
+    const int ngroups = A.S_packed / 32;
+    const int g0 = split * A.gps, g1 = (g0 + A.gps < ngroups) ? g0 + A.gps : ngroups;
+    const int npk = g1 > g0 ? g1 - g0 : 0;
+    const int ntc = (split == A.nsplit - 1) ? (A.tail_len + 31) / 32 : 0;      // the last split also takes the tail, 32 tokens at a time
+
+    for (int it = wv; it < npk + ntc; it += 4) {
+        float sc[NP][GMAX];
+        if (it < npk) {                                               // ---- a packed group
+            const int gi = g0 + it;
+            const uint8_t* ksp = A.ks + (bh * (A.S_cap / 32) + gi) * D + c * 8;
+            const uint2 ksr = *reinterpret_cast<const uint2*>(ksp);
+            uint32_t kr[NP][2], vr[NP][2], vsb[NP];
+            float bv[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const int tok = gi * 32 + p * TP + ts;
+                const int64_t row = bh * A.S_cap + tok;
+                if (FP4) {
+                    kr[p][0] = *reinterpret_cast<const uint32_t*>(A.kc + row * (D / 2) + c * CB); kr[p][1] = 0u;
+                    vr[p][0] = *reinterpret_cast<const uint32_t*>(A.vc + row * (D / 2) + c * CB); vr[p][1] = 0u;
+                } else {
+                    const uint2 kk = *reinterpret_cast<const uint2*>(A.kc + row * D + c * CB); kr[p][0] = kk.x; kr[p][1] = kk.y;
+                    const uint2 vv = *reinterpret_cast<const uint2*>(A.vc + row * D + c * CB); vr[p][0] = vv.x; vr[p][1] = vv.y;
+                }
+                vsb[p] = A.vs[row * (D / 32) + c / 4];
+                bv[p] = A.bias ? A.bias[(int64_t)b * stot + tok] : 0.f;
+            }
+            float ksf[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ksf[j] = e8m0_f32(((j < 4 ? ksr.x : ksr.y) >> (8 * (j & 3))) & 0xFFu);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                float kf[8];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {                         // channel pairs: the K scales differ inside a pair, so scale 1 and an exact multiply
+                    v2f_t v;
+                    if (FP4) {
+                        if (j == 0) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(kr[p][0], 1.0f, 0);
+                        else if (j == 1) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(kr[p][0], 1.0f, 1);
+                        else if (j == 2) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(kr[p][0], 1.0f, 2);
+                        else v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(kr[p][0], 1.0f, 3);
+                    } else {
+                        if ((j & 1) == 0) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(kr[p][j >> 1], 1.0f, false);
+                        else v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(kr[p][j >> 1], 1.0f, true);
+                    }
+                    kf[2 * j] = v[0] * ksf[2 * j]; kf[2 * j + 1] = v[1] * ksf[2 * j + 1];
+                }
+#pragma unroll
+                for (int g = 0; g < GMAX; ++g) {
+                    float dot = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) dot = __builtin_fmaf(q[g][j], kf[j], dot);
+#pragma unroll
+                    for (int o = 1; o < LPT; o <<= 1) dot += __shfl_xor(dot, o, 64);
+                    sc[p][g] = __builtin_fmaf(dot, A.scaling, bv[p]);
+                }
+            }
+            softmax_fold<NP, GMAX>(sc, m, l, acc);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const float vsc = u2f(vsb[p] << 23);                  // a V block lies along head_dim: the pair shares the scale operand
+                float vf[8];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    v2f_t v;
+                    if (FP4) {
+                        if (j == 0) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(vr[p][0], vsc, 0);
+                        else if (j == 1) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(vr[p][0], vsc, 1);
+                        else if (j == 2) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(vr[p][0], vsc, 2);
+                        else v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(vr[p][0], vsc, 3);
+                    } else {
+                        if ((j & 1) == 0) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(vr[p][j >> 1], vsc, false);
+                        else v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(vr[p][j >> 1], vsc, true);
+                    }
+                    vf[2 * j] = v[0]; vf[2 * j + 1] = v[1];
+                }
+#pragma unroll
+                for (int g = 0; g < GMAX; ++g)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[g][j] = __builtin_fmaf(sc[p][g], vf[j], acc[g][j]);
+            }
+        } else {                                                      // ---- 32 tokens of the tail (cache dtype = the query's)
+            const int tc = it - npk;
+            uint4 kr[NP], vr[NP];
+            float bv[NP];
+            bool ok[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const int j = tc * 32 + p * TP + ts;
+                ok[p] = j < A.tail_len;
+                kr[p] = make_uint4(0u, 0u, 0u, 0u); vr[p] = make_uint4(0u, 0u, 0u, 0u); bv[p] = 0.f;
+                if (ok[p]) {
+                    const int64_t e = (bh * A.tail_cap + j) * D + c * 8;
+                    kr[p] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(A.kt) + e);
+                    vr[p] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(A.vt) + e);
+                    if (A.bias) bv[p] = A.bias[(int64_t)b * stot + A.S_packed + j];
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const uint32_t w[4] = {kr[p].x, kr[p].y, kr[p].z, kr[p].w};
+                float kf[8];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { kf[2 * j] = half_lo(w[j], QDT); kf[2 * j + 1] = half_hi(w[j], QDT); }
+#pragma unroll
+                for (int g = 0; g < GMAX; ++g) {
+                    float dot = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) dot = __builtin_fmaf(q[g][j], kf[j], dot);
+#pragma unroll
+                    for (int o = 1; o < LPT; o <<= 1) dot += __shfl_xor(dot, o, 64);
+                    sc[p][g] = ok[p] ? __builtin_fmaf(dot, A.scaling, bv[p]) : neg_inf();
+                }
+            }
+            softmax_fold<NP, GMAX>(sc, m, l, acc);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const uint32_t w[4] = {vr[p].x, vr[p].y, vr[p].z, vr[p].w};       // zeros where the token does not exist
+                float vf[8];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { vf[2 * j] = half_lo(w[j], QDT); vf[2 * j + 1] = half_hi(w[j], QDT); }
+#pragma unroll
+                for (int g = 0; g < GMAX; ++g)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[g][j] = __builtin_fmaf(sc[p][g], vf[j], acc[g][j]);
+            }
+        }
+    }
+
+    // the TP token subsets of the wave -> lanes 0 .. LPT - 1
+#pragma unroll
+    for (int o = LPT; o < 64; o <<= 1) {
+#pragma unroll
+        for (int g = 0; g < GMAX; ++g) {
+            const float mo = __shfl_xor(m[g], o, 64), lo = __shfl_xor(l[g], o, 64);
+            const float mn = __builtin_fmaxf(m[g], mo);
+            const float mm = (mn == neg_inf()) ? 0.f : mn;
+            const float a = ex(m[g] - mm), bb = ex(mo - mm);
+            l[g] = l[g] * a + lo * bb;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float ao = __shfl_xor(acc[g][j], o, 64); acc[g][j] = acc[g][j] * a + ao * bb; }
+            m[g] = mn;
+        }
+    }
+    if (ts == 0) {
+#pragma unroll
+        for (int g = 0; g < GMAX; ++g) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) red[wv][g][c * 8 + j] = acc[g][j];
+            if (c == 0) { red[wv][g][D] = m[g]; red[wv][g][D + 1] = l[g]; }
+        }
+    }
+    __syncthreads();
+    // the four waves, in wave order -> the split's partial (acc[D], m, l) of every query head of the group
+    for (int idx = threadIdx.x; idx < G * D; idx += 256) {
+        const int g = idx / D, d = idx % D;
+        float mn = neg_inf();
+#pragma unroll
+        for (int w = 0; w < 4; ++w) mn = __builtin_fmaxf(mn, red[w][g][D]);
+        const float mm = (mn == neg_inf()) ? 0.f : mn;
+        float num = 0.f, den = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const float f = ex(red[w][g][D] - mm); num += red[w][g][d] * f; den += red[w][g][D + 1] * f; }
+        float* o = A.ws + ((((int64_t)b * A.Hq + hk * G + g) * A.nsplit) + split) * (D + 2);
+        o[d] = num;
+        if (d == 0) { o[D] = mn; o[D + 1] = den; }
+    }
+}
+
+// the splits of one (sequence, query head) in ascending order; a row whose every position is masked gives zeros
+template <int D, int ODT>
+__global__ void __launch_bounds__(D)
+k_kvp_attn_combine(const float* __restrict__ ws, void* __restrict__ out, int nsplit) {
+    const int d = threadIdx.x;
+    const int64_t row = blockIdx.x;                                   // b * Hq + hq
+    const float* p = ws + row * nsplit * (D + 2);
+    float mn = neg_inf();
+    for (int s = 0; s < nsplit; ++s) mn = __builtin_fmaxf(mn, p[s * (D + 2) + D]);
+    const float mm = (mn == neg_inf()) ? 0.f : mn;
+    float num = 0.f, den = 0.f;
+    for (int s = 0; s < nsplit; ++s) {
+        const float f = ex(p[s * (D + 2) + D] - mm);
+        num += p[s * (D + 2) + d] * f; den += p[s * (D + 2) + D + 1] * f;
+    }
+    const float y = den > 0.f ? num / den : 0.f;
+    if (ODT == 0) reinterpret_cast<float*>(out)[row * D + d] = y;
+    else if (ODT == 1) reinterpret_cast<uint16_t*>(out)[row * D + d] = __builtin_bit_cast(uint16_t, (_Float16)y);
+    else reinterpret_cast<uint16_t*>(out)[row * D + d] = __builtin_bit_cast(uint16_t, (__bf16)y);
+}
+
+int kvp_fail(int code, const char* msg) { msq_set_error_(msg); return code; }
+
+// Token splits of the decode kernel: a function of S_packed alone (not of the batch or the head count), so a sequence gives the same bits
+// whatever it is batched with.  A split is a whole number of groups of 32, a multiple of 4 groups (one per wave), at most 64 splits.
+struct AttnPlan { int nsplit, gps; };
+int attn_plan(int64_t B, int Hq, int Hkv, int D, int64_t S_packed, int64_t tail_len, AttnPlan* p) {
+    if (B <= 0 || Hq <= 0 || Hkv <= 0 || S_packed < 0 || tail_len < 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: sizes must be positive");
+    if (Hq % Hkv) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: Hq must be a multiple of Hkv");
+    if (Hq / Hkv > 8) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn: at most 8 query heads per kv head");
+    if (D != 64 && D != 128) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn: head_dim must be 64 or 128");
+    if (S_packed % 32) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: S_packed must be a multiple of 32");
+    if (S_packed + tail_len == 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: the cache is empty");
+    if (S_packed > (int64_t)1 << 30 || tail_len > (int64_t)1 << 20 || B > 65535 || Hkv > 65535)
+        return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn: sizes beyond the launch grid");
+    const int64_t ng = S_packed / 32;
+    int64_t gps = (ng + 63) / 64;
+    gps = (gps + 3) / 4 * 4;
+    if (gps < 4) gps = 4;
+    p->gps = (int)gps;
+    p->nsplit = ng ? (int)((ng + gps - 1) / gps) : 1;
+    return MSQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msq_kv_mx_pack(const void* in, int dtype, void* codes, void* scales, int64_t B, int64_t H, int64_t T, int64_t D, int64_t S_cap,
+                   int64_t pos, int elem_fmt, int along_tokens, int* status_flag, void* stream) {
+    if (B < 0 || H < 0 || T < 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_pack: negative size");
+    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_pack: elem_fmt must be fp8_e4m3 or fp4_e2m1");
+    if (dtype < 0 || dtype > 2) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_pack: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+    if (D <= 0 || D % 32 || D > 256) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_pack: head_dim must be a multiple of 32, at most 256");
+    if (S_cap <= 0 || S_cap % 32) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_pack: S_cap must be a positive multiple of 32");
+    if (T % 32) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_pack: T must be a multiple of 32");
+    if (pos < 0 || pos % 32) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_pack: pos must be a multiple of 32");
+    if (pos + T > S_cap) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_pack: pos + T exceeds S_cap");
+    if (B * H * T == 0) return MSQ_OK;
+    if (!in || !codes || !scales) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_pack: null buffer");
+    if ((((uintptr_t)in | (uintptr_t)codes) & 15) != 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_pack: buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const bool f4 = elem_fmt == MSQ_FMT_FP4_E2M1;
+    const int64_t total = along_tokens ? B * H * (T / 32) * D : B * H * T * (D / 32);
+    if ((total + 255) / 256 > 0x7FFFFFFF) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_pack: tensor too large for one launch");
+    const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
+#define MSQ_KVP(K, DTV, F4) hipLaunchKernelGGL((K<DTV, F4>), grid, blk, 0, st, in, (uint8_t*)codes, (uint8_t*)scales, total, T, (int)D, S_cap, pos, status_flag)
+#define MSQ_KVP_DT(K, F4) do { if (dtype == 0) MSQ_KVP(K, 0, F4); else if (dtype == 1) MSQ_KVP(K, 1, F4); else MSQ_KVP(K, 2, F4); } while (0)
+    if (along_tokens) { if (f4) MSQ_KVP_DT(k_kvp_pack_k, true); else MSQ_KVP_DT(k_kvp_pack_k, false); }
+    else { if (f4) MSQ_KVP_DT(k_kvp_pack_v, true); else MSQ_KVP_DT(k_kvp_pack_v, false); }
+#undef MSQ_KVP_DT
+#undef MSQ_KVP
+    return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_pack: launch failed");
+}
+
+int msq_kv_mx_unpack(const void* codes, const void* scales, void* out, int dtype, int64_t B, int64_t H, int64_t D, int64_t S_cap,
+                     int64_t pos, int64_t T, int elem_fmt, int along_tokens, void* stream) {
+    if (B < 0 || H < 0 || T < 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_unpack: negative size");
+    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_unpack: elem_fmt must be fp8_e4m3 or fp4_e2m1");
+    if (dtype < 0 || dtype > 2) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_unpack: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
+    if (D <= 0 || D % 32 || D > 256) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_unpack: head_dim must be a multiple of 32, at most 256");
+    if (S_cap <= 0 || S_cap % 32) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_unpack: S_cap must be a positive multiple of 32");
+    if (pos < 0 || pos + T > S_cap) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_unpack: pos + T exceeds S_cap");
+    if (B * H * T == 0) return MSQ_OK;
+    if (!codes || !scales || !out) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_unpack: null buffer");
+    if ((((uintptr_t)out | (uintptr_t)codes) & 15) != 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_unpack: buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const bool f4 = elem_fmt == MSQ_FMT_FP4_E2M1;
+    const int64_t total = B * H * T * (D / 2);
+    if ((total + 255) / 256 > 0x7FFFFFFF) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_unpack: tensor too large for one launch");
+    const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
+#define MSQ_KVU(DTV, F4) hipLaunchKernelGGL((k_kvp_unpack<DTV, F4>), grid, blk, 0, st, (const uint8_t*)codes, (const uint8_t*)scales, out, total, T, (int)D, S_cap, pos, along_tokens ? 1 : 0)
+#define MSQ_KVU_DT(F4) do { if (dtype == 0) MSQ_KVU(0, F4); else if (dtype == 1) MSQ_KVU(1, F4); else MSQ_KVU(2, F4); } while (0)
+    if (f4) MSQ_KVU_DT(true); else MSQ_KVU_DT(false);
+#undef MSQ_KVU_DT
+#undef MSQ_KVU
+    return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_unpack: launch failed");
+}
+
+int msq_kv_mx_attn_plan(int64_t B, int Hq, int Hkv, int D, int64_t S_packed, int64_t tail_len, int* n_splits, int* split_tokens,
+                        int64_t* workspace_bytes) {
+    AttnPlan p;
+    const int rc = attn_plan(B, Hq, Hkv, D, S_packed, tail_len, &p);
+    if (rc != MSQ_OK) return rc;
+    if (n_splits) *n_splits = p.nsplit;
+    if (split_tokens) *split_tokens = p.gps * 32;
+    if (workspace_bytes) *workspace_bytes = B * Hq * (int64_t)p.nsplit * (D + 2) * (int64_t)sizeof(float);
+    return MSQ_OK;
+}
+
+int64_t msq_kv_mx_attn_workspace_bytes(int64_t B, int Hq, int Hkv, int D, int64_t S_packed, int64_t tail_len) {
+    int64_t bytes = 0;
+    const int rc = msq_kv_mx_attn_plan(B, Hq, Hkv, D, S_packed, tail_len, nullptr, nullptr, &bytes);
+    return rc != MSQ_OK ? (int64_t)rc : bytes;
+}
+
+int msq_kv_mx_attn_decode(const void* q, int q_dtype, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                          int64_t S_packed, int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_len, int64_t tail_cap,
+                          const float* bias, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt, float scaling,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+    AttnPlan p;
+    const int rc = attn_plan(B, Hq, Hkv, D, S_packed, tail_len, &p);
+    if (rc != MSQ_OK) return rc;
+    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode: elem_fmt must be fp8_e4m3 or fp4_e2m1");
+    if (q_dtype != 1 && q_dtype != 2) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode: q and the tail must be f16 (1) or bf16 (2)");
+    if (out_dtype != 0 && out_dtype != q_dtype) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode: out must be float32 or the q dtype");
+    if (S_cap < 0 || S_cap % 32 || S_packed > S_cap) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: S_packed exceeds S_cap (a multiple of 32)");
+    if (tail_len > tail_cap) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: tail_len exceeds tail_cap");
+    if (!q || !out || !workspace) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: null buffer");
+    if (S_packed && (!k_codes || !k_scales || !v_codes || !v_scales)) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: null buffer (planes)");
+    if (tail_len && (!k_tail || !v_tail)) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: null buffer (tail)");
+    const int64_t need = B * Hq * (int64_t)p.nsplit * (D + 2) * (int64_t)sizeof(float);
+    if (workspace_bytes < need) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: workspace too small (msq_kv_mx_attn_workspace_bytes)");
+    if ((((uintptr_t)q | (uintptr_t)k_codes | (uintptr_t)k_scales | (uintptr_t)v_codes | (uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)workspace) & 15) != 0)
+        return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: buffers must be 16-byte aligned");
+    AttnArgs A;
+    A.q = q; A.kc = (const uint8_t*)k_codes; A.ks = (const uint8_t*)k_scales; A.vc = (const uint8_t*)v_codes; A.vs = (const uint8_t*)v_scales;
+    A.kt = k_tail; A.vt = v_tail; A.bias = bias; A.ws = (float*)workspace;
+    A.Hq = Hq; A.G = Hq / Hkv; A.nsplit = p.nsplit; A.gps = p.gps; A.S_packed = (int)S_packed; A.tail_len = (int)tail_len; A.tail_cap = (int)tail_cap;
+    A.S_cap = S_cap; A.scaling = scaling;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)p.nsplit, (unsigned)Hkv, (unsigned)B), blk(256);
+    const bool f4 = elem_fmt == MSQ_FMT_FP4_E2M1;
+    const int gm = A.G <= 1 ? 1 : (A.G <= 2 ? 2 : (A.G <= 4 ? 4 : 8));
+#define MSQ_KVA(DV, F4, GM, QD) hipLaunchKernelGGL((k_kvp_attn_split<DV, F4, GM, QD>), grid, blk, 0, st, A)
+#define MSQ_KVA_Q(DV, F4, GM) do { if (q_dtype == 1) MSQ_KVA(DV, F4, GM, 1); else MSQ_KVA(DV, F4, GM, 2); } while (0)
+#define MSQ_KVA_G(DV, F4) do { if (gm == 1) MSQ_KVA_Q(DV, F4, 1); else if (gm == 2) MSQ_KVA_Q(DV, F4, 2); else if (gm == 4) MSQ_KVA_Q(DV, F4, 4); else MSQ_KVA_Q(DV, F4, 8); } while (0)
+#define MSQ_KVA_F(DV) do { if (f4) MSQ_KVA_G(DV, true); else MSQ_KVA_G(DV, false); } while (0)
+    if (D == 64) MSQ_KVA_F(64); else MSQ_KVA_F(128);
+#undef MSQ_KVA_F
+#undef MSQ_KVA_G
+#undef MSQ_KVA_Q
+#undef MSQ_KVA
+    if (hipGetLastError() != hipSuccess) return kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_attn_decode: launch failed");
+    const dim3 cgrid((unsigned)(B * Hq));
+#define MSQ_KVC(DV) do { if (out_dtype == 0) hipLaunchKernelGGL((k_kvp_attn_combine<DV, 0>), cgrid, dim3(DV), 0, st, (const float*)workspace, out, p.nsplit); \
+                         else if (out_dtype == 1) hipLaunchKernelGGL((k_kvp_attn_combine<DV, 1>), cgrid, dim3(DV), 0, st, (const float*)workspace, out, p.nsplit); \
+                         else hipLaunchKernelGGL((k_kvp_attn_combine<DV, 2>), cgrid, dim3(DV), 0, st, (const float*)workspace, out, p.nsplit); } while (0)
+    if (D == 64) MSQ_KVC(64); else MSQ_KVC(128);
+#undef MSQ_KVC
+    return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_attn_decode: launch failed");
+}
+
+}  // extern "C"
