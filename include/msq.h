@@ -66,6 +66,7 @@ extern "C" {
 /* status bits written to *status_flag by the outlier kernels */
 #define MSQ_STATUS_NAN 1 /* one of the reference's NaN asserts (utils/quant.py:225-250) would fire */
 #define MSQ_STATUS_INEXACT 2 /* pack: a value is not exactly code * 2^scale (never silently wrong) */
+#define MSQ_STATUS_OVERFLOW 8 /* msq_kv_mx_append_dev: the packed cache was full (or its state was not a valid one); the token was dropped */
 #define MSQ_STATUS_TIMEOUT 4 /* msq_gptq_block: a workgroup gave up waiting at the grid barrier (CUs held by another stream or process): the result is invalid */
 
 /* GEMM-ready plane kinds (what the fused kernel converts in-register with the CDNA4
@@ -507,8 +508,29 @@ int msq_kv_group_quant(const void* in, void* out, int dtype, int64_t B, int64_t 
  *                     min((s + 1) * split_tokens, S_packed), the last one also the tail; a function of S_packed alone, so a sequence gives
  *                     the same bits whatever it is batched with.  Any output pointer may be NULL.
  *   msq_kv_mx_attn_workspace_bytes   the plan's workspace size (B Hq n_splits (D + 2) floats), or a negative MSQ_ERR_*.
- * Not built: lengths held on the device (and with them HIP-graph capture of a step), paged / block-table caches, prefill attention over
- * the codes, MicroScopiQ outlier caches, more than one query token.
+ *
+ * Lengths held on the device: a fixed-capacity cache whose single-token decode step -- append, then attention -- has
+ * launch arguments and grids that do not depend on the lengths, so the step can be captured in a HIP graph and replayed.
+ *   state             int32[4] in device memory, 16-byte aligned, one per layer: {packed_len, tail_len, status, 0}.  All sequences of a layer
+ *                     share the lengths.  status collects MSQ_STATUS_NAN (a flushed block held Inf / NaN) and MSQ_STATUS_OVERFLOW.
+ *   msq_kv_mx_append_dev    one token k_new / v_new [B, H, 1, D] (dtype 1 f16 or 2 bf16, the dtype of the tail) per sequence, by the rule of
+ *                     msq.kvpacked.PackedKV.append at one token, read from `state`: if tail_len == tail_cap the tail (k_tail / v_tail
+ *                     [B, H, tail_cap, D]) is packed into the planes at packed_len (the bytes msq_kv_mx_pack writes), packed_len += tail_cap
+ *                     and tail_len = 0; then the token goes to tail slot tail_len and tail_len += 1.  If the flush would need
+ *                     packed_len + tail_cap > S_cap nothing is written, the lengths stay and MSQ_STATUS_OVERFLOW is raised (also for a
+ *                     state that is not a valid one: a negative length, tail_len > tail_cap, packed_len no multiple of 32 or > S_cap).
+ *                     S_cap % 32 == 0, tail_cap % 32 == 0.  Four launches on `stream` whose grids depend on (B, H, D, tail_cap) only:
+ *                     flush K, flush V, the token, and one thread that moves the lengths after every reader of the old ones; no host read.
+ *   msq_kv_mx_attn_plan_cap max_splits = the largest n_splits msq_kv_mx_attn_plan gives for any S_packed <= S_cap (at most 64; not the plan
+ *                     of S_cap itself: above 8192 tokens a longer cache may take fewer splits) and the workspace of a device-length call,
+ *                     B Hq max_splits (D + 2) floats.  Host arithmetic.  Either output pointer may be NULL.
+ *   msq_kv_mx_attn_decode_dev   msq_kv_mx_attn_decode with S_packed and tail_len read from `state` by the kernels: grid (max_splits, Hkv, B),
+ *                     every block derives the plan of the lengths it finds (the same function as msq_kv_mx_attn_plan) and blocks beyond
+ *                     the live splits return, so for equal cache contents the output equals msq_kv_mx_attn_decode's bit for bit.  An
+ *                     empty cache gives zeros.  bias [B, bias_stride] f32 or NULL, indexed by the absolute token position (packed tokens,
+ *                     then the tail); bias_stride >= S_cap + tail_cap; entries at or beyond the length are never read.  Lengths found
+ *                     outside 0 .. S_cap / 0 .. tail_cap are cut to them.
+ * Not built: paged / block-table caches, prefill attention over the codes, MicroScopiQ outlier caches, more than one query token.
  * ------------------------------------------------------------------------- */
 int msq_kv_mx_pack(const void* in, int dtype, void* codes, void* scales, int64_t B, int64_t H, int64_t T, int64_t D, int64_t S_cap,
                    int64_t pos, int elem_fmt, int along_tokens, int* status_flag, void* stream);
@@ -521,6 +543,14 @@ int msq_kv_mx_attn_decode(const void* q, int q_dtype, const void* k_codes, const
                           int64_t S_packed, int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_len, int64_t tail_cap,
                           const float* bias, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt, float scaling,
                           void* workspace, int64_t workspace_bytes, void* stream);
+int msq_kv_mx_append_dev(const void* k_new, const void* v_new, int dtype, void* k_codes, void* k_scales, void* v_codes, void* v_scales,
+                         int64_t S_cap, void* k_tail, void* v_tail, int64_t tail_cap, int* state, int64_t B, int64_t H, int64_t D, int elem_fmt,
+                         void* stream);
+int msq_kv_mx_attn_plan_cap(int64_t B, int Hq, int Hkv, int D, int64_t S_cap, int64_t tail_cap, int* max_splits, int64_t* workspace_bytes);
+int msq_kv_mx_attn_decode_dev(const void* q, int q_dtype, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                              int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_cap, const int* state, const float* bias,
+                              int64_t bias_stride, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt, float scaling,
+                              void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Bfloat-rounded vector ops around the MX Linear.  The reference emulates every non-GEMM op as the

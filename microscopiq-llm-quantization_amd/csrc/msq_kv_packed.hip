@@ -17,6 +17,10 @@
 // has seen (no cross-lane traffic in the loop beyond the dot product's butterfly), merged across the lanes of a wave by shuffles and
 // across the four waves through LDS in a fixed order; every split writes (acc[D], m, l) to the workspace and a second launch combines the
 // splits in ascending order.  No atomics, no flags, no block waits on another: equal inputs give equal bits.
+//
+// Lengths on the device: msq_kv_mx_append_dev / msq_kv_mx_attn_decode_dev read {packed_len, tail_len} from an int32[4] state
+// in device memory instead of taking them as launch arguments, with grids fixed by the capacity, so that a decode step can be captured in a
+// HIP graph.  They are further instantiations of the kernels below (template switches DEVPOS / DEV): the host-length forms are unchanged.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -79,11 +83,32 @@ MSQ_D void mx_block32(const float (&a)[32], uint32_t (&cw)[FP4 ? 4 : 8], int& sb
     }
 }
 
+// ---- device-held lengths: state = int32[4] {packed_len, tail_len, status, 0} of one layer, read by every block of a launch
+// and changed only by k_kvp_advance, a launch of its own behind every reader on the stream.
+// What a single-token append does in the state it finds: 0 nothing (the cache is full, or the state is not one this library wrote),
+// 1 the token goes to tail slot `slot`, 2 the full tail is packed at token `pos` first and the token goes to slot 0.
+MSQ_D int append_step(const int* state, int64_t S_cap, int tail_cap, int& pos, int& slot) {
+    const int pl = __builtin_amdgcn_readfirstlane(state[0]), tl = __builtin_amdgcn_readfirstlane(state[1]);
+    pos = pl; slot = tl;
+    if (pl < 0 || pl % 32 || pl > S_cap || tl < 0 || tl > tail_cap) return 0;
+    if (tl < tail_cap) return 1;
+    if ((int64_t)pl + tail_cap > S_cap) return 0;
+    slot = 0;
+    return 2;
+}
+
 // ---- pack, K form: one lane per (b h, token group, channel), channel fastest: 32 strided reads, coalesced across the lanes
-template <int DT, bool FP4>
+// DEVPOS (both pack kernels): the flush of msq_kv_mx_append_dev.  `in` is the tail [B H, T = tail_cap, D]; the position comes from `state`, the
+// launch does nothing unless the tail is full and fits, and the status bits go to state[2].
+template <int DT, bool FP4, bool DEVPOS = false>
 __global__ void __launch_bounds__(256)
 k_kvp_pack_k(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t total, int64_t T, int D,
-             int64_t S_cap, int64_t pos, int* status_flag) {
+             int64_t S_cap, int64_t pos, int* status_flag, int* state) {
+    if (DEVPOS) {
+        int p, slot;
+        if (append_step(state, S_cap, (int)T, p, slot) != 2) return;
+        pos = p; status_flag = state + 2;
+    }
     const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool live = t0 < total;                                   // total is even and so is D: a nibble pair is live or dead as one
     const int64_t t = live ? t0 : 0;
@@ -117,10 +142,15 @@ k_kvp_pack_k(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* 
 }
 
 // ---- pack, V form: one lane per (b h, token, block of 32 channels): 16-byte reads and stores
-template <int DT, bool FP4>
+template <int DT, bool FP4, bool DEVPOS = false>
 __global__ void __launch_bounds__(256)
 k_kvp_pack_v(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t total, int64_t T, int D,
-             int64_t S_cap, int64_t pos, int* status_flag) {
+             int64_t S_cap, int64_t pos, int* status_flag, int* state) {
+    if (DEVPOS) {
+        int p, slot;
+        if (append_step(state, S_cap, (int)T, p, slot) != 2) return;
+        pos = p; status_flag = state + 2;
+    }
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
     const int nb = D / 32;
@@ -192,7 +222,30 @@ struct AttnArgs {
     int Hq, G, nsplit, gps, S_packed, tail_len, tail_cap;
     int64_t S_cap;
     float scaling;
+    const int* state; int bias_stride;            // the device-length form (DEV): lengths from state, bias rows of bias_stride floats
 };
+
+// Token splits of the decode kernel: a function of the packed groups alone (not of the batch or the head count), so a sequence gives the same
+// bits whatever it is batched with.  A split is a whole number of groups of 32, a multiple of 4 groups (one per wave), at most 64 splits.
+// The one statement of the rule: the host plan and the device-length kernels both call it.
+struct AttnPlan { int nsplit, gps; };
+MSQ_HD AttnPlan attn_split_plan(int64_t ng) {
+    int64_t gps = (ng + 63) / 64;
+    gps = (gps + 3) / 4 * 4;
+    if (gps < 4) gps = 4;
+    AttnPlan p;
+    p.gps = (int)gps;
+    p.nsplit = ng ? (int)((ng + gps - 1) / gps) : 1;
+    return p;
+}
+
+// the lengths a device-length launch works with: whatever the state holds, cut to the planes and the tail it was given
+MSQ_D void dev_lengths(const int* state, int64_t S_cap, int tail_cap, int& S_packed, int& tail_len) {
+    int pl = __builtin_amdgcn_readfirstlane(state[0]), tl = __builtin_amdgcn_readfirstlane(state[1]);
+    pl = pl < 0 ? 0 : (pl > S_cap ? (int)S_cap : pl);
+    S_packed = pl & ~31;
+    tail_len = tl < 0 ? 0 : (tl > tail_cap ? tail_cap : tl);
+}
 
 constexpr float LOG2E = 1.44269504088896340736f;
 MSQ_D float ex(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }                 // e^x; e^-inf = 0
@@ -219,7 +272,9 @@ MSQ_D void softmax_fold(float (&sc)[NP][GMAX], float (&m)[GMAX], float (&l)[GMAX
     }
 }
 
-template <int D, bool FP4, int GMAX, int QDT>
+// DEV: the grid is (max_splits of the capacity, Hkv, B); every block reads the lengths from A.state, derives the plan a host-length launch at
+// those lengths gets and returns when its split does not exist, so the live blocks do what that launch's blocks do, bit for bit.
+template <int D, bool FP4, int GMAX, int QDT, bool DEV = false>
 __global__ void __launch_bounds__(256)
 k_kvp_attn_split(const AttnArgs A) {
     constexpr int LPT = D / 8, TP = 64 / LPT, NP = 32 / TP;          // lanes per token, tokens per pass of a wave, passes per group of 32
@@ -230,7 +285,14 @@ k_kvp_attn_split(const AttnArgs A) {
     const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
     const int G = A.G, Hkv = A.Hq / G;
     const int64_t bh = (int64_t)b * Hkv + hk;
-    const int stot = A.S_packed + A.tail_len;
+    int S_packed = A.S_packed, tail_len = A.tail_len, nsplit = A.nsplit, gps = A.gps;
+    if (DEV) {
+        dev_lengths(A.state, A.S_cap, A.tail_cap, S_packed, tail_len);
+        const AttnPlan pl = attn_split_plan(S_packed / 32);
+        nsplit = pl.nsplit; gps = pl.gps;
+        if (split >= nsplit) return;
+    }
+    const int stot = DEV ? A.bias_stride : S_packed + tail_len;      // floats of a bias row
 
     float q[GMAX][8];
 #pragma unroll
@@ -249,10 +311,10 @@ k_kvp_attn_split(const AttnArgs A) {
         for (int j = 0; j < 8; ++j) acc[g][j] = 0.f;
     }
 
-    const int ngroups = A.S_packed / 32;
-    const int g0 = split * A.gps, g1 = (g0 + A.gps < ngroups) ? g0 + A.gps : ngroups;
+    const int ngroups = S_packed / 32;
+    const int g0 = split * gps, g1 = (g0 + gps < ngroups) ? g0 + gps : ngroups;
     const int npk = g1 > g0 ? g1 - g0 : 0;
-    const int ntc = (split == A.nsplit - 1) ? (A.tail_len + 31) / 32 : 0;      // the last split also takes the tail, 32 tokens at a time
+    const int ntc = (split == nsplit - 1) ? (tail_len + 31) / 32 : 0;      // the last split also takes the tail, 32 tokens at a time
 
     for (int it = wv; it < npk + ntc; it += 4) {
         float sc[NP][GMAX];
@@ -338,13 +400,13 @@ k_kvp_attn_split(const AttnArgs A) {
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 const int j = tc * 32 + p * TP + ts;
-                ok[p] = j < A.tail_len;
+                ok[p] = j < tail_len;
                 kr[p] = make_uint4(0u, 0u, 0u, 0u); vr[p] = make_uint4(0u, 0u, 0u, 0u); bv[p] = 0.f;
                 if (ok[p]) {
                     const int64_t e = (bh * A.tail_cap + j) * D + c * 8;
                     kr[p] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(A.kt) + e);
                     vr[p] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(A.vt) + e);
-                    if (A.bias) bv[p] = A.bias[(int64_t)b * stot + A.S_packed + j];
+                    if (A.bias) bv[p] = A.bias[(int64_t)b * stot + S_packed + j];
                 }
             }
 #pragma unroll
@@ -412,16 +474,22 @@ k_kvp_attn_split(const AttnArgs A) {
         float num = 0.f, den = 0.f;
 #pragma unroll
         for (int w = 0; w < 4; ++w) { const float f = ex(red[w][g][D] - mm); num += red[w][g][d] * f; den += red[w][g][D + 1] * f; }
-        float* o = A.ws + ((((int64_t)b * A.Hq + hk * G + g) * A.nsplit) + split) * (D + 2);
+        float* o = A.ws + ((((int64_t)b * A.Hq + hk * G + g) * nsplit) + split) * (D + 2);
         o[d] = num;
         if (d == 0) { o[D] = mn; o[D + 1] = den; }
     }
 }
 
 // the splits of one (sequence, query head) in ascending order; a row whose every position is masked gives zeros
-template <int D, int ODT>
+// DEV: the number of live splits comes from the state, as in k_kvp_attn_split
+template <int D, int ODT, bool DEV = false>
 __global__ void __launch_bounds__(D)
-k_kvp_attn_combine(const float* __restrict__ ws, void* __restrict__ out, int nsplit) {
+k_kvp_attn_combine(const float* __restrict__ ws, void* __restrict__ out, int nsplit, const int* state, int64_t S_cap) {
+    if (DEV) {
+        int S_packed, tail_len;
+        dev_lengths(state, S_cap, 0, S_packed, tail_len);
+        nsplit = attn_split_plan(S_packed / 32).nsplit;
+    }
     const int d = threadIdx.x;
     const int64_t row = blockIdx.x;                                   // b * Hq + hq
     const float* p = ws + row * nsplit * (D + 2);
@@ -441,9 +509,6 @@ k_kvp_attn_combine(const float* __restrict__ ws, void* __restrict__ out, int nsp
 
 int kvp_fail(int code, const char* msg) { msq_set_error_(msg); return code; }
 
-// Token splits of the decode kernel: a function of S_packed alone (not of the batch or the head count), so a sequence gives the same bits
-// whatever it is batched with.  A split is a whole number of groups of 32, a multiple of 4 groups (one per wave), at most 64 splits.
-struct AttnPlan { int nsplit, gps; };
 int attn_plan(int64_t B, int Hq, int Hkv, int D, int64_t S_packed, int64_t tail_len, AttnPlan* p) {
     if (B <= 0 || Hq <= 0 || Hkv <= 0 || S_packed < 0 || tail_len < 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: sizes must be positive");
     if (Hq % Hkv) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: Hq must be a multiple of Hkv");
@@ -453,13 +518,56 @@ int attn_plan(int64_t B, int Hq, int Hkv, int D, int64_t S_packed, int64_t tail_
     if (S_packed + tail_len == 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: the cache is empty");
     if (S_packed > (int64_t)1 << 30 || tail_len > (int64_t)1 << 20 || B > 65535 || Hkv > 65535)
         return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn: sizes beyond the launch grid");
-    const int64_t ng = S_packed / 32;
-    int64_t gps = (ng + 63) / 64;
-    gps = (gps + 3) / 4 * 4;
-    if (gps < 4) gps = 4;
-    p->gps = (int)gps;
-    p->nsplit = ng ? (int)((ng + gps - 1) / gps) : 1;
+    *p = attn_split_plan(S_packed / 32);
     return MSQ_OK;
+}
+
+// ---- the single-token append of the device-length cache (msq_kv_mx_append_dev), after the flush: one lane per 16 bytes of the token
+__global__ void __launch_bounds__(256)
+k_kvp_tail_put(const uint4* __restrict__ k_new, const uint4* __restrict__ v_new, uint4* __restrict__ k_tail, uint4* __restrict__ v_tail, int64_t total,
+               int dv, int64_t S_cap, int tail_cap, const int* state) {
+    int pos, slot;
+    if (append_step(state, S_cap, tail_cap, pos, slot) == 0) return;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int64_t bh = t / dv, dst = (bh * tail_cap + slot) * dv + t % dv;       // k_new / v_new [B H, 1, D], the tail [B H, tail_cap, D]
+    k_tail[dst] = k_new[t];
+    v_tail[dst] = v_new[t];
+}
+
+// ... and the lengths: one lane, a launch of its own behind every kernel that read the old ones
+__global__ void __launch_bounds__(64)
+k_kvp_advance(int* state, int64_t S_cap, int tail_cap) {
+    if (threadIdx.x) return;
+    int pos, slot;
+    const int step = append_step(state, S_cap, tail_cap, pos, slot);
+    if (step == 0) { atomicOr(state + 2, MSQ_STATUS_OVERFLOW); return; }
+    if (step == 2) state[0] = pos + tail_cap;
+    state[1] = slot + 1;
+}
+
+// the two launches of a decode call (DEV: the device-length form, grid_x = the capacity's max_splits)
+template <bool DEV>
+int attn_launch(const AttnArgs& A, int q_dtype, void* out, int out_dtype, int64_t B, int Hkv, int D, bool f4, int grid_x, hipStream_t st, const char* fail) {
+    const dim3 grid((unsigned)grid_x, (unsigned)Hkv, (unsigned)B), blk(256);
+    const int gm = A.G <= 1 ? 1 : (A.G <= 2 ? 2 : (A.G <= 4 ? 4 : 8));
+#define MSQ_KVA(DV, F4, GM, QD) hipLaunchKernelGGL((k_kvp_attn_split<DV, F4, GM, QD, DEV>), grid, blk, 0, st, A)
+#define MSQ_KVA_Q(DV, F4, GM) do { if (q_dtype == 1) MSQ_KVA(DV, F4, GM, 1); else MSQ_KVA(DV, F4, GM, 2); } while (0)
+#define MSQ_KVA_G(DV, F4) do { if (gm == 1) MSQ_KVA_Q(DV, F4, 1); else if (gm == 2) MSQ_KVA_Q(DV, F4, 2); else if (gm == 4) MSQ_KVA_Q(DV, F4, 4); else MSQ_KVA_Q(DV, F4, 8); } while (0)
+#define MSQ_KVA_F(DV) do { if (f4) MSQ_KVA_G(DV, true); else MSQ_KVA_G(DV, false); } while (0)
+    if (D == 64) MSQ_KVA_F(64); else MSQ_KVA_F(128);
+#undef MSQ_KVA_F
+#undef MSQ_KVA_G
+#undef MSQ_KVA_Q
+#undef MSQ_KVA
+    if (hipGetLastError() != hipSuccess) return kvp_fail(MSQ_ERR_LAUNCH, fail);
+    const dim3 cgrid((unsigned)(B * A.Hq));
+#define MSQ_KVC1(DV, OD) hipLaunchKernelGGL((k_kvp_attn_combine<DV, OD, DEV>), cgrid, dim3(DV), 0, st, (const float*)A.ws, out, A.nsplit, A.state, A.S_cap)
+#define MSQ_KVC(DV) do { if (out_dtype == 0) MSQ_KVC1(DV, 0); else if (out_dtype == 1) MSQ_KVC1(DV, 1); else MSQ_KVC1(DV, 2); } while (0)
+    if (D == 64) MSQ_KVC(64); else MSQ_KVC(128);
+#undef MSQ_KVC
+#undef MSQ_KVC1
+    return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, fail);
 }
 
 }  // namespace
@@ -484,7 +592,7 @@ int msq_kv_mx_pack(const void* in, int dtype, void* codes, void* scales, int64_t
     const int64_t total = along_tokens ? B * H * (T / 32) * D : B * H * T * (D / 32);
     if ((total + 255) / 256 > 0x7FFFFFFF) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_pack: tensor too large for one launch");
     const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
-#define MSQ_KVP(K, DTV, F4) hipLaunchKernelGGL((K<DTV, F4>), grid, blk, 0, st, in, (uint8_t*)codes, (uint8_t*)scales, total, T, (int)D, S_cap, pos, status_flag)
+#define MSQ_KVP(K, DTV, F4) hipLaunchKernelGGL((K<DTV, F4>), grid, blk, 0, st, in, (uint8_t*)codes, (uint8_t*)scales, total, T, (int)D, S_cap, pos, status_flag, (int*)nullptr)
 #define MSQ_KVP_DT(K, F4) do { if (dtype == 0) MSQ_KVP(K, 0, F4); else if (dtype == 1) MSQ_KVP(K, 1, F4); else MSQ_KVP(K, 2, F4); } while (0)
     if (along_tokens) { if (f4) MSQ_KVP_DT(k_kvp_pack_k, true); else MSQ_KVP_DT(k_kvp_pack_k, false); }
     else { if (f4) MSQ_KVP_DT(k_kvp_pack_v, true); else MSQ_KVP_DT(k_kvp_pack_v, false); }
@@ -557,28 +665,83 @@ int msq_kv_mx_attn_decode(const void* q, int q_dtype, const void* k_codes, const
     A.q = q; A.kc = (const uint8_t*)k_codes; A.ks = (const uint8_t*)k_scales; A.vc = (const uint8_t*)v_codes; A.vs = (const uint8_t*)v_scales;
     A.kt = k_tail; A.vt = v_tail; A.bias = bias; A.ws = (float*)workspace;
     A.Hq = Hq; A.G = Hq / Hkv; A.nsplit = p.nsplit; A.gps = p.gps; A.S_packed = (int)S_packed; A.tail_len = (int)tail_len; A.tail_cap = (int)tail_cap;
-    A.S_cap = S_cap; A.scaling = scaling;
+    A.S_cap = S_cap; A.scaling = scaling; A.state = nullptr; A.bias_stride = 0;
+    return attn_launch<false>(A, q_dtype, out, out_dtype, B, Hkv, D, elem_fmt == MSQ_FMT_FP4_E2M1, p.nsplit, (hipStream_t)stream, "msq_kv_mx_attn_decode: launch failed");
+}
+
+int msq_kv_mx_attn_plan_cap(int64_t B, int Hq, int Hkv, int D, int64_t S_cap, int64_t tail_cap, int* max_splits, int64_t* workspace_bytes) {
+    AttnPlan p;
+    const int rc = attn_plan(B, Hq, Hkv, D, 0, 1, &p);           // the checks of the sizes that do not depend on a length
+    if (rc != MSQ_OK) return rc;
+    if (S_cap < 0 || S_cap % 32 || S_cap > (int64_t)1 << 30) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_plan_cap: S_cap must be a multiple of 32, at most 2^30");
+    if (tail_cap <= 0 || tail_cap % 32 || tail_cap > (int64_t)1 << 20) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_plan_cap: tail_cap must be a positive multiple of 32");
+    // n_splits is not monotone in the length (above 8192 tokens a longer cache may take fewer, larger splits), so this is the maximum over
+    // every length the planes can hold; 64 is the rule's ceiling, reached at 8192 tokens at the latest
+    int ms = 1;
+    for (int64_t ng = 1; ng <= S_cap / 32 && ms < 64; ++ng) { const int n = attn_split_plan(ng).nsplit; ms = n > ms ? n : ms; }
+    if (max_splits) *max_splits = ms;
+    if (workspace_bytes) *workspace_bytes = B * Hq * (int64_t)ms * (D + 2) * (int64_t)sizeof(float);
+    return MSQ_OK;
+}
+
+int msq_kv_mx_attn_decode_dev(const void* q, int q_dtype, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                              int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_cap, const int* state, const float* bias,
+                              int64_t bias_stride, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt, float scaling,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+    int ms = 0;
+    int64_t need = 0;
+    const int rc = msq_kv_mx_attn_plan_cap(B, Hq, Hkv, D, S_cap, tail_cap, &ms, &need);
+    if (rc != MSQ_OK) return rc;
+    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode_dev: elem_fmt must be fp8_e4m3 or fp4_e2m1");
+    if (q_dtype != 1 && q_dtype != 2) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode_dev: q and the tail must be f16 (1) or bf16 (2)");
+    if (out_dtype != 0 && out_dtype != q_dtype) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode_dev: out must be float32 or the q dtype");
+    if (!state) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: null state");
+    if (bias && (bias_stride < S_cap + tail_cap || bias_stride > 0x7FFFFFFF))
+        return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: bias_stride must be at least S_cap + tail_cap");
+    if (!q || !out || !workspace || !k_tail || !v_tail) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: null buffer");
+    if (S_cap && (!k_codes || !k_scales || !v_codes || !v_scales)) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: null buffer (planes)");
+    if (workspace_bytes < need) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: workspace too small (msq_kv_mx_attn_plan_cap)");
+    if ((((uintptr_t)q | (uintptr_t)k_codes | (uintptr_t)k_scales | (uintptr_t)v_codes | (uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)workspace | (uintptr_t)state) & 15) != 0)
+        return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: buffers must be 16-byte aligned");
+    AttnArgs A;
+    A.q = q; A.kc = (const uint8_t*)k_codes; A.ks = (const uint8_t*)k_scales; A.vc = (const uint8_t*)v_codes; A.vs = (const uint8_t*)v_scales;
+    A.kt = k_tail; A.vt = v_tail; A.bias = bias; A.ws = (float*)workspace;
+    A.Hq = Hq; A.G = Hq / Hkv; A.nsplit = 0; A.gps = 0; A.S_packed = 0; A.tail_len = 0; A.tail_cap = (int)tail_cap;
+    A.S_cap = S_cap; A.scaling = scaling; A.state = state; A.bias_stride = (int)bias_stride;
+    return attn_launch<true>(A, q_dtype, out, out_dtype, B, Hkv, D, elem_fmt == MSQ_FMT_FP4_E2M1, ms, (hipStream_t)stream, "msq_kv_mx_attn_decode_dev: launch failed");
+}
+
+int msq_kv_mx_append_dev(const void* k_new, const void* v_new, int dtype, void* k_codes, void* k_scales, void* v_codes, void* v_scales,
+                         int64_t S_cap, void* k_tail, void* v_tail, int64_t tail_cap, int* state, int64_t B, int64_t H, int64_t D, int elem_fmt,
+                         void* stream) {
+    if (B <= 0 || H <= 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: sizes must be positive");
+    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_append_dev: elem_fmt must be fp8_e4m3 or fp4_e2m1");
+    if (dtype != 1 && dtype != 2) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_append_dev: the cache dtype must be f16 (1) or bf16 (2)");
+    if (D <= 0 || D % 32 || D > 256) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_append_dev: head_dim must be a multiple of 32, at most 256");
+    if (S_cap <= 0 || S_cap % 32 || S_cap > (int64_t)1 << 30) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: S_cap must be a positive multiple of 32, at most 2^30");
+    if (tail_cap <= 0 || tail_cap % 32 || tail_cap > (int64_t)1 << 20) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: tail_cap must be a positive multiple of 32");
+    if (!state) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: null state");
+    if (!k_new || !v_new || !k_codes || !k_scales || !v_codes || !v_scales || !k_tail || !v_tail) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: null buffer");
+    if ((((uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_codes | (uintptr_t)v_codes | (uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)state) & 15) != 0)
+        return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: buffers must be 16-byte aligned");
+    const int64_t tot_k = B * H * (tail_cap / 32) * D, tot_v = B * H * tail_cap * (D / 32), tot_p = B * H * (D / 8);
+    if ((tot_k + 255) / 256 > 0x7FFFFFFF || (tot_v + 255) / 256 > 0x7FFFFFFF) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_append_dev: tensor too large for one launch");
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)p.nsplit, (unsigned)Hkv, (unsigned)B), blk(256);
     const bool f4 = elem_fmt == MSQ_FMT_FP4_E2M1;
-    const int gm = A.G <= 1 ? 1 : (A.G <= 2 ? 2 : (A.G <= 4 ? 4 : 8));
-#define MSQ_KVA(DV, F4, GM, QD) hipLaunchKernelGGL((k_kvp_attn_split<DV, F4, GM, QD>), grid, blk, 0, st, A)
-#define MSQ_KVA_Q(DV, F4, GM) do { if (q_dtype == 1) MSQ_KVA(DV, F4, GM, 1); else MSQ_KVA(DV, F4, GM, 2); } while (0)
-#define MSQ_KVA_G(DV, F4) do { if (gm == 1) MSQ_KVA_Q(DV, F4, 1); else if (gm == 2) MSQ_KVA_Q(DV, F4, 2); else if (gm == 4) MSQ_KVA_Q(DV, F4, 4); else MSQ_KVA_Q(DV, F4, 8); } while (0)
-#define MSQ_KVA_F(DV) do { if (f4) MSQ_KVA_G(DV, true); else MSQ_KVA_G(DV, false); } while (0)
-    if (D == 64) MSQ_KVA_F(64); else MSQ_KVA_F(128);
-#undef MSQ_KVA_F
-#undef MSQ_KVA_G
-#undef MSQ_KVA_Q
-#undef MSQ_KVA
-    if (hipGetLastError() != hipSuccess) return kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_attn_decode: launch failed");
-    const dim3 cgrid((unsigned)(B * Hq));
-#define MSQ_KVC(DV) do { if (out_dtype == 0) hipLaunchKernelGGL((k_kvp_attn_combine<DV, 0>), cgrid, dim3(DV), 0, st, (const float*)workspace, out, p.nsplit); \
-                         else if (out_dtype == 1) hipLaunchKernelGGL((k_kvp_attn_combine<DV, 1>), cgrid, dim3(DV), 0, st, (const float*)workspace, out, p.nsplit); \
-                         else hipLaunchKernelGGL((k_kvp_attn_combine<DV, 2>), cgrid, dim3(DV), 0, st, (const float*)workspace, out, p.nsplit); } while (0)
-    if (D == 64) MSQ_KVC(64); else MSQ_KVC(128);
-#undef MSQ_KVC
-    return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_attn_decode: launch failed");
+    const dim3 blk(256), gk((unsigned)((tot_k + 255) / 256)), gv((unsigned)((tot_v + 255) / 256)), gp((unsigned)((tot_p + 255) / 256));
+    // four launches, every grid a function of (B, H, D, tail_cap) alone: the flush (K form, V form: no-ops unless the tail is full and fits), the
+    // token into its slot, and the one thread that moves the lengths once every reader of the old ones is done
+#define MSQ_KVF(K, DTV, F4, G, TAIL, C, SC, TOT) hipLaunchKernelGGL((K<DTV, F4, true>), G, blk, 0, st, (const void*)TAIL, (uint8_t*)C, (uint8_t*)SC, TOT, tail_cap, (int)D, S_cap, (int64_t)0, (int*)nullptr, state)
+#define MSQ_KVF_DT(K, F4, G, TAIL, C, SC, TOT) do { if (dtype == 1) MSQ_KVF(K, 1, F4, G, TAIL, C, SC, TOT); else MSQ_KVF(K, 2, F4, G, TAIL, C, SC, TOT); } while (0)
+    if (f4) { MSQ_KVF_DT(k_kvp_pack_k, true, gk, k_tail, k_codes, k_scales, tot_k); MSQ_KVF_DT(k_kvp_pack_v, true, gv, v_tail, v_codes, v_scales, tot_v); }
+    else { MSQ_KVF_DT(k_kvp_pack_k, false, gk, k_tail, k_codes, k_scales, tot_k); MSQ_KVF_DT(k_kvp_pack_v, false, gv, v_tail, v_codes, v_scales, tot_v); }
+#undef MSQ_KVF_DT
+#undef MSQ_KVF
+    if (hipGetLastError() != hipSuccess) return kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_append_dev: launch failed");
+    hipLaunchKernelGGL(k_kvp_tail_put, gp, blk, 0, st, (const uint4*)k_new, (const uint4*)v_new, (uint4*)k_tail, (uint4*)v_tail, tot_p, (int)(D / 8), S_cap,
+                       (int)tail_cap, (const int*)state);
+    hipLaunchKernelGGL(k_kvp_advance, dim3(1), dim3(64), 0, st, state, S_cap, (int)tail_cap);
+    return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_append_dev: launch failed");
 }
 
 }  // extern "C"

@@ -9,11 +9,15 @@ values it holds and an unpack rounds once to the cache dtype -- not the in-dtype
 results are not always code x 2^e (parity table).
 
   PackedKV            one layer's storage (planes + a tail of tokens that do not fill a group yet), independent of transformers
+  StaticPackedKV      the same with a fixed capacity and the lengths in device memory: a decode step -- append(k, v), then
+                      attend_dev(q) -- launches the same kernels with the same arguments at every length, so it can be captured in a HIP
+                      graph and replayed; the host keeps a mirror of the lengths that every Python call advances without a device read
   PackedMXKVCache     a transformers Cache whose layers wrap PackedKV; update() returns dequantize(), so any attention works
   use_packed_attention registers the attention function "msq_packed_kv" and ties a model's attention modules to the cache's layers
 
-Not built: lengths held on the device / HIP-graph capture of a step, paged or block-table caches, prefill attention over the codes,
-MicroScopiQ outlier caches, more than one query token.  Every entry raises MsqError on CPU tensors: there is no CPU fallback."""
+Not built: paged or block-table caches, prefill attention over the codes, MicroScopiQ outlier caches, more than one query token, capture of
+a whole transformers model (its mask and position plumbing is not ours: PackedMXKVCache(max_len=...) runs eagerly).  Every entry raises
+MsqError on CPU tensors: there is no CPU fallback."""
 import ctypes as C
 
 import torch
@@ -25,6 +29,7 @@ _FMT = {"fp8_e4m3": 5, "fp4_e2m1": 8, "fp4": 8}                  # include/msq.h
 _CODE_BITS = {5: 8, 8: 4}
 GROUP = 32                                                       # the MX block: tokens of a K block, channels of a V block
 ATTENTION_NAME = "msq_packed_kv"
+STATUS_NAN, STATUS_OVERFLOW = 1, 8                               # include/msq.h MSQ_STATUS_*
 
 
 def _fmt_id(elem_format):
@@ -260,6 +265,178 @@ class PackedKV:
         return plane_nbytes(self.B, self.Hkv, self.capacity, self.D, self.elem_format) + 2 * self.B * self.Hkv * self.gap * self.D * esz
 
 
+def attn_plan_cap(B, Hq, Hkv, D, S_cap, tail_cap):
+    """(max_splits, workspace_bytes) of the device-length decode entry for planes of S_cap tokens: the largest n_splits of attn_plan over
+    every S_packed <= S_cap (host arithmetic)."""
+    ms, wb = C.c_int(-1), C.c_int64(-1)
+    check(lib().msq_kv_mx_attn_plan_cap(B, Hq, Hkv, D, S_cap, tail_cap, C.byref(ms), C.byref(wb)), "msq_kv_mx_attn_plan_cap")
+    return ms.value, wb.value
+
+
+class StaticPackedKV(PackedKV):
+    """PackedKV with planes allocated once for `max_len` tokens (rounded up to a multiple of `gap`) and the lengths held on the device:
+    ``state`` = int32[4] {packed_len, tail_len, status, 0}.
+
+    A single-token ``append`` and ``attend_dev`` read the lengths from ``state`` inside their kernels; their launches do not depend on the
+    lengths, so the pair can be captured in a HIP graph (one stream, a linear chain) and replayed.  ``packed_len`` / ``tail_len`` are the
+    host's mirror: every Python call advances them arithmetically, never by a device read.  A replay does not go through Python: call
+    ``advance_host(n)`` after n replayed steps, or ``sync()`` to read the state back (which also raises on a status bit).  A warm-up before
+    capture moves the lengths like any other step: undo it with ``set_lengths``."""
+
+    def __init__(self, B, Hkv, D, dtype, elem_format="fp8_e4m3", gap=32, max_len=256, device="cuda"):
+        if gap <= 0 or gap % GROUP:
+            raise MsqError("StaticPackedKV: gap must be a positive multiple of 32")
+        if max_len <= 0:
+            raise MsqError("StaticPackedKV: max_len must be positive")
+        self.S_cap = (int(max_len) + gap - 1) // gap * gap
+        self._ws_dev = {}                                        # Hq -> workspace: never replaced, a captured graph holds its address
+        self._bias_pad = None
+        super().__init__(B, Hkv, D, dtype, elem_format, gap, self.S_cap, device)
+        self._alloc_state()
+
+    # ---- storage and launches (overridden by the host test's stub) -----------------------------------------------------------------
+    def _reserve(self, need):
+        if need > self.S_cap:
+            raise MsqError("StaticPackedKV: %d packed tokens exceed the capacity of %d" % (need, self.S_cap))
+        if self.planes is None:
+            self._alloc_planes()
+
+    def _alloc_planes(self):
+        self.planes = {n: torch.zeros(s, dtype=torch.uint8, device=self.device)
+                       for n, s in plane_shapes(self.B, self.Hkv, self.S_cap, self.D, self.elem_format).items()}
+        self.capacity = self.S_cap
+
+    def _alloc_state(self):
+        self.state = torch.zeros(4, dtype=torch.int32, device=self.device)
+
+    def _write_state(self, clear_status=False):
+        """one host-to-device copy: the mirror's lengths (and, with clear_status, zeros for the status word)"""
+        if clear_status:
+            self.state.copy_(torch.tensor([self.packed_len, self.tail_len, 0, 0], dtype=torch.int32))
+        else:
+            self.state[:2].copy_(torch.tensor([self.packed_len, self.tail_len], dtype=torch.int32))
+
+    def _read_state(self):
+        return self.state.tolist()                               # one device-to-host copy
+
+    def _capturing(self):
+        return torch.cuda.is_current_stream_capturing()
+
+    def _append_dev(self, k, v):
+        k, v = k.contiguous(), v.contiguous()
+        if k.data_ptr() % 16 or v.data_ptr() % 16:
+            if self._capturing():
+                raise MsqError("StaticPackedKV.append: k and v must be 16-byte aligned during capture")
+            k, v = k.clone(), v.clone()
+        p = self.planes
+        check(lib().msq_kv_mx_append_dev(ptr(k), ptr(v), _DT[self.dtype], ptr(p["k_codes"]), ptr(p["k_scales"]), ptr(p["v_codes"]),
+                                         ptr(p["v_scales"]), self.S_cap, ptr(self.k_tail), ptr(self.v_tail), self.gap, ptr(self.state),
+                                         self.B, self.Hkv, self.D, self.fmt_id, current_stream(self.device)), "msq_kv_mx_append_dev")
+
+    # ---- the cache ------------------------------------------------------------------------------------------------------------------
+    def _after_steps(self, n):
+        """the mirror's lengths after n single-token appends (the rule of PackedKV.append, in closed form)"""
+        if n <= 0:
+            return self.packed_len, self.tail_len
+        t = self.tail_len + n
+        flushes = (t - 1) // self.gap
+        packed = self.packed_len + flushes * self.gap
+        if packed > self.S_cap:
+            raise MsqError("StaticPackedKV: %d more token(s) overflow the capacity of %d packed tokens (MSQ_STATUS_OVERFLOW on the device)"
+                           % (n, self.S_cap))
+        return packed, t - flushes * self.gap
+
+    def advance_host(self, n=1):
+        """apply n single-token steps to the host mirror (after n replays of a captured step); no device access"""
+        self.packed_len, self.tail_len = self._after_steps(int(n))
+
+    def append(self, k, v):
+        self._check_kv(k, v)
+        T = k.shape[2]
+        if T == 0:
+            return
+        if T == 1:
+            after = self._after_steps(1)                         # raises before any launch when the mirror knows the cache is full
+            self._append_dev(k, v)
+            self.packed_len, self.tail_len = after
+            return
+        if self._capturing():
+            raise MsqError("StaticPackedKV.append: a multi-token append runs on host lengths and cannot be captured")
+        super().append(k, v)
+        self._write_state()
+
+    def set_lengths(self, packed_len, tail_len):
+        """mirror and device state := (packed_len, tail_len), status cleared: restore after a warm-up, roll back"""
+        packed_len, tail_len = int(packed_len), int(tail_len)
+        if packed_len < 0 or packed_len % self.gap or packed_len > self.S_cap or not 0 <= tail_len <= self.gap:
+            raise MsqError("StaticPackedKV.set_lengths: packed_len must be a multiple of gap within the capacity, tail_len within the tail")
+        self.packed_len, self.tail_len = packed_len, tail_len
+        self._write_state(clear_status=True)
+
+    def sync(self):
+        """read the device state back (one copy): the mirror takes its lengths; a status bit raises MsqError (set_lengths clears it)"""
+        packed_len, tail_len, status, _ = self._read_state()
+        self.packed_len, self.tail_len = int(packed_len), int(tail_len)
+        if status & STATUS_OVERFLOW:
+            raise MsqError("StaticPackedKV: MSQ_STATUS_OVERFLOW (an append found the cache full and dropped the token)")
+        if status & STATUS_NAN:
+            raise MsqError("StaticPackedKV: MSQ_STATUS_NAN (a packed block holds Inf / NaN)")
+        if status:
+            raise MsqError("StaticPackedKV: status %d" % status)
+        return self.packed_len, self.tail_len
+
+    def attend_dev(self, q, bias=None, scaling=None, out_dtype=None):
+        """attend() with the lengths read from the device state by the kernels: the same bits as attend() at equal lengths, zeros for an
+        empty cache.  bias [B, W] float32, indexed by the absolute token position; W >= S_cap + gap is used in place (entries at or beyond
+        the length are never read; this is the form to capture), a narrower one must be [B, len] of the mirror and is copied into a buffer
+        of that width first.  The workspace is allocated on the first call for a given Hq: run one eager call before capturing."""
+        _need_cuda(q, bias)
+        if q.ndim == 4 and q.shape[2] == 1:
+            q = q[:, :, 0, :]
+        if q.ndim != 3 or q.shape[0] != self.B or q.shape[2] != self.D or q.dtype != self.dtype:
+            raise MsqError("StaticPackedKV.attend_dev: expected q [%d, Hq, %d] of %s" % (self.B, self.D, self.dtype))
+        Hq = q.shape[1]
+        out_dtype = q.dtype if out_dtype is None else out_dtype
+        if out_dtype not in (q.dtype, torch.float32):
+            raise MsqError("StaticPackedKV.attend_dev: out_dtype must be the q dtype or float32")
+        capturing = self._capturing()
+        if not q.is_contiguous() or q.data_ptr() % 16:
+            q = q.contiguous()
+            if q.data_ptr() % 16:
+                q = q.clone()
+        width = self.S_cap + self.gap
+        if bias is not None:
+            if bias.ndim != 2 or bias.shape[0] != self.B:
+                raise MsqError("StaticPackedKV.attend_dev: bias must be [%d, W]" % self.B)
+            if bias.shape[1] >= width:
+                if bias.dtype != torch.float32 or not bias.is_contiguous():
+                    bias = bias.to(torch.float32).contiguous()
+            else:
+                if bias.shape[1] != self.len:
+                    raise MsqError("StaticPackedKV.attend_dev: bias must be [%d, %d] (the length) or at least %d wide" % (self.B, self.len, width))
+                if self._bias_pad is None:
+                    if capturing:
+                        raise MsqError("StaticPackedKV.attend_dev: pass a bias at least %d wide during capture" % width)
+                    self._bias_pad = torch.zeros(self.B, width, dtype=torch.float32, device=self.device)
+                self._bias_pad[:, :bias.shape[1]] = bias
+                bias = self._bias_pad
+        scaling = float(self.D) ** -0.5 if scaling is None else float(scaling)
+        ws = self._ws_dev.get(Hq)
+        if ws is None:
+            if capturing:
+                raise MsqError("StaticPackedKV.attend_dev: the workspace is not allocated yet: run one eager attend_dev call before capturing")
+            ws = self._ws_dev[Hq] = torch.empty(attn_plan_cap(self.B, Hq, self.Hkv, self.D, self.S_cap, self.gap)[1], dtype=torch.uint8,
+                                                device=self.device)
+        out = torch.empty(self.B, Hq, self.D, dtype=out_dtype, device=self.device)
+        p = self.planes
+        check(lib().msq_kv_mx_attn_decode_dev(ptr(q), _DT[q.dtype], ptr(p["k_codes"]), ptr(p["k_scales"]), ptr(p["v_codes"]), ptr(p["v_scales"]),
+                                              self.S_cap, ptr(self.k_tail), ptr(self.v_tail), self.gap, ptr(self.state), ptr(bias),
+                                              bias.shape[1] if bias is not None else 0, ptr(out), _DT[out_dtype], self.B, Hq, self.Hkv,
+                                              self.D, self.fmt_id, scaling, ptr(ws), ws.numel(), current_stream(self.device)),
+              "msq_kv_mx_attn_decode_dev")
+        return out
+
+
 def _make_layer_class():
     from transformers.cache_utils import CacheLayerMixin
 
@@ -269,9 +446,9 @@ def _make_layer_class():
         is_sliding = False
         is_compileable = False
 
-        def __init__(self, elem_format="fp8_e4m3", gap=32, capacity=256):
+        def __init__(self, elem_format="fp8_e4m3", gap=32, capacity=256, max_len=None):
             super().__init__()
-            self.elem_format, self.gap, self.capacity = elem_format, gap, capacity
+            self.elem_format, self.gap, self.capacity, self.max_len = elem_format, gap, capacity, max_len
             self.packed = None
             self.fused = False
 
@@ -279,7 +456,10 @@ def _make_layer_class():
             _need_cuda(key_states)
             B, H, _, D = key_states.shape
             self.dtype, self.device = key_states.dtype, key_states.device
-            self.packed = PackedKV(B, H, D, key_states.dtype, self.elem_format, self.gap, self.capacity, key_states.device)
+            if self.max_len is None:
+                self.packed = PackedKV(B, H, D, key_states.dtype, self.elem_format, self.gap, self.capacity, key_states.device)
+            else:                                                # fixed capacity, lengths on the device: a one-token update is the device append
+                self.packed = StaticPackedKV(B, H, D, key_states.dtype, self.elem_format, self.gap, self.max_len, key_states.device)
             self.keys = self.values = None
             self.is_initialized = True
 
@@ -304,20 +484,26 @@ def _make_layer_class():
             return -1
 
         def reset(self):
-            if self.packed is not None:
+            if isinstance(self.packed, StaticPackedKV):
+                self.packed.set_lengths(0, 0)
+            elif self.packed is not None:
                 self.packed.packed_len = self.packed.tail_len = 0
 
     return PackedKVLayer
 
 
-def PackedMXKVCache(num_layers, elem_format="fp8_e4m3", gap=32, capacity=256):
-    """A transformers Cache (``past_key_values=PackedMXKVCache(n)``) whose layers hold packed MX planes."""
+def PackedMXKVCache(num_layers, elem_format="fp8_e4m3", gap=32, capacity=256, max_len=None):
+    """A transformers Cache (``past_key_values=PackedMXKVCache(n)``) whose layers hold packed MX planes.  With ``max_len`` the layers are
+    StaticPackedKV (fixed capacity, lengths on the device): a one-token update() is the device append, get_seq_length() comes from the host
+    mirror without a sync, and the tied attention function calls attend_dev."""
     from transformers.cache_utils import Cache
     layer_cls = _make_layer_class()
     _fmt_id(elem_format)
     if gap <= 0 or gap % GROUP:
         raise MsqError("PackedMXKVCache: gap must be a positive multiple of 32")
-    return Cache(layers=[layer_cls(elem_format, gap, capacity) for _ in range(num_layers)])
+    if max_len is not None and max_len <= 0:
+        raise MsqError("PackedMXKVCache: max_len must be positive")
+    return Cache(layers=[layer_cls(elem_format, gap, capacity, max_len) for _ in range(num_layers)])
 
 
 def _packed_attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None, **kwargs):
@@ -336,7 +522,10 @@ def _packed_attention_forward(module, query, key, value, attention_mask, dropout
             bias = am.to(torch.float32)
         if bias.shape[0] != query.shape[0]:
             bias = bias.expand(query.shape[0], -1)
-    out = layer.packed.attend(query[:, :, 0, :], bias, scaling)
+    if isinstance(layer.packed, StaticPackedKV):                 # lengths from the device state; bias_stride = the mask length
+        out = layer.packed.attend_dev(query[:, :, 0, :], bias, scaling)
+    else:
+        out = layer.packed.attend(query[:, :, 0, :], bias, scaling)
     return out.unsqueeze(1), None                                # [B, 1, Hq, D], the layout the attention interface returns
 
 
