@@ -530,7 +530,21 @@ int msq_kv_group_quant(const void* in, void* out, int dtype, int64_t B, int64_t 
  *                     empty cache gives zeros.  bias [B, bias_stride] f32 or NULL, indexed by the absolute token position (packed tokens,
  *                     then the tail); bias_stride >= S_cap + tail_cap; entries at or beyond the length are never read.  Lengths found
  *                     outside 0 .. S_cap / 0 .. tail_cap are cut to them.
- * Not built: paged / block-table caches, prefill attention over the codes, MicroScopiQ outlier caches, more than one query token.
+ *
+ * More than one query token: causal attention of the LAST T tokens the cache holds over the codes, on the matrix cores.
+ *   msq_kv_mx_attn_multi    out[b, t, hq, :] = softmax(scaling q[b, hq, t, :] K^T + bias + causal) V over the packed tokens 0 .. S_packed and
+ *                     then the tail, as msq_kv_mx_attn_decode.  q [B, Hq, T, D] f16 / bf16 (the dtype of the tail), 1 <= T <= 32,
+ *                     T <= S_packed + tail_len; with causal != 0 query t sees the positions <= S_packed + tail_len - T + t.  bias f32 or NULL,
+ *                     may hold -inf: bias_row_stride_t == 0 reads rows [B, len] (one row for every t), otherwise rows [B, T, bias_row_stride_t]
+ *                     (bias_row_stride_t >= len).  A row whose every position is masked gives zeros.  out [B, T, Hq, D] in out_dtype = q_dtype
+ *                     or 0 (f32; the half output is the f32 output rounded once).  Hq / Hkv <= 8, D 64 or 128.  A block owns (sequence, kv head,
+ *                     token split, row tile of at most 64 (token, head) rows); the splits are msq_kv_mx_attn_plan's.  Codes and scales are
+ *                     decoded exactly to bf16 operands of v_mfma_f32_16x16x32_bf16, an fp16 q and the probabilities are split into hi + lo
+ *                     parts; fp32 online softmax.  Values below the smallest normal bf16 (2^-126) are outside the contract.  Two launches, no
+ *                     atomics: equal inputs give equal bits, and a row's bits do not depend on the rows it is computed with.
+ *   msq_kv_mx_attn_multi_workspace_bytes   B Hq T n_splits (D + 2) floats, or a negative MSQ_ERR_*.
+ * Not built: paged / block-table caches, prefill attention over the codes (more than 32 query tokens), MicroScopiQ outlier caches, a
+ * device-length (_dev) form of msq_kv_mx_attn_multi and a device-side multi-token append.
  * ------------------------------------------------------------------------- */
 int msq_kv_mx_pack(const void* in, int dtype, void* codes, void* scales, int64_t B, int64_t H, int64_t T, int64_t D, int64_t S_cap,
                    int64_t pos, int elem_fmt, int along_tokens, int* status_flag, void* stream);
@@ -551,6 +565,11 @@ int msq_kv_mx_attn_decode_dev(const void* q, int q_dtype, const void* k_codes, c
                               int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_cap, const int* state, const float* bias,
                               int64_t bias_stride, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt, float scaling,
                               void* workspace, int64_t workspace_bytes, void* stream);
+int64_t msq_kv_mx_attn_multi_workspace_bytes(int64_t B, int Hq, int Hkv, int D, int T, int64_t S_packed, int64_t tail_len);
+int msq_kv_mx_attn_multi(const void* q, int q_dtype, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                         int64_t S_packed, int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_len, int64_t tail_cap,
+                         const float* bias, int64_t bias_row_stride_t, int causal, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D,
+                         int T, int elem_fmt, float scaling, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Bfloat-rounded vector ops around the MX Linear.  The reference emulates every non-GEMM op as the

@@ -15,9 +15,14 @@ results are not always code x 2^e (parity table).
   PackedMXKVCache     a transformers Cache whose layers wrap PackedKV; update() returns dequantize(), so any attention works
   use_packed_attention registers the attention function "msq_packed_kv" and ties a model's attention modules to the cache's layers
 
-Not built: paged or block-table caches, prefill attention over the codes, MicroScopiQ outlier caches, more than one query token, capture of
-a whole transformers model (its mask and position plumbing is not ours: PackedMXKVCache(max_len=...) runs eagerly).  Every entry raises
-MsqError on CPU tensors: there is no CPU fallback."""
+Query lengths 2 .. 32: ``PackedKV.attend_multi`` is causal attention of the LAST T tokens the cache holds over the codes on
+the matrix cores (csrc/msq_kv_packed_multi.hip) -- a few draft tokens to verify, a short chunk of new tokens -- and ``PackedKV.crop`` takes
+rejected tokens back.  ``use_packed_attention(model, cache, max_query_tokens=T)`` routes those lengths to it.
+
+Not built: paged or block-table caches, prefill attention over the codes (more than 32 query tokens go to sdpa on the dequantised tensors),
+MicroScopiQ outlier caches, a device-length form of attend_multi and a device-side multi-token append (both run on the host mirror's lengths
+and cannot be captured), capture of a whole transformers model (its mask and position plumbing is not ours: PackedMXKVCache(max_len=...)
+runs eagerly).  Every entry raises MsqError on CPU tensors: there is no CPU fallback."""
 import ctypes as C
 
 import torch
@@ -28,6 +33,7 @@ _DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 _FMT = {"fp8_e4m3": 5, "fp4_e2m1": 8, "fp4": 8}                  # include/msq.h MSQ_FMT_*
 _CODE_BITS = {5: 8, 8: 4}
 GROUP = 32                                                       # the MX block: tokens of a K block, channels of a V block
+MAX_QUERY_TOKENS = 32                                            # of attend_multi (msq_kv_mx_attn_multi)
 ATTENTION_NAME = "msq_packed_kv"
 STATUS_NAN, STATUS_OVERFLOW = 1, 8                               # include/msq.h MSQ_STATUS_*
 
@@ -125,6 +131,7 @@ class PackedKV:
         self.packed_len = self.tail_len = self.capacity = 0
         self.planes = None
         self._ws = None
+        self._ws_multi = None                                    # attend_multi's workspace
         self._alloc_tail()
         self._reserve(max(int(capacity), GROUP))
 
@@ -253,6 +260,79 @@ class PackedKV:
                                           ptr(self._ws), self._ws.numel(), current_stream(self.device)), "msq_kv_mx_attn_decode")
         return out
 
+    def _capturing(self):
+        return False
+
+    def _unpack(self, pos, T):
+        """K and V of the packed tokens pos .. pos + T in the cache dtype"""
+        k = mx_unpack(self.planes["k_codes"], self.planes["k_scales"], pos, T, self.D, self.dtype, self.elem_format, True)
+        v = mx_unpack(self.planes["v_codes"], self.planes["v_scales"], pos, T, self.D, self.dtype, self.elem_format, False)
+        return k, v
+
+    def crop(self, n):
+        """keep the first n tokens (0 <= n <= len): dequantize() of those is the same bits before and after.  n in the tail: tail_len
+        changes.  n < packed_len: packed_len := n - n % gap and the tail becomes the unpacked codes packed_len .. n (the values dequantize()
+        gave for them); the planes before packed_len are not touched."""
+        n = int(n)
+        if not 0 <= n <= self.len:
+            raise MsqError("PackedKV.crop: n must be 0 .. %d (the cached length), not %d" % (self.len, n))
+        if self._capturing():
+            raise MsqError("PackedKV.crop runs on host lengths and cannot be captured")
+        if n >= self.packed_len:
+            self.tail_len = n - self.packed_len
+            return
+        packed = n - n % self.gap
+        rest = n - packed
+        if rest:
+            k, v = self._unpack(packed, rest)
+            self._tail_put(k, v, 0)
+        self.packed_len, self.tail_len = packed, rest
+
+    def attend_multi(self, q, bias=None, causal=True, scaling=None, out_dtype=None):
+        """softmax(scaling q K^T + bias + causal) V for the LAST T tokens the cache holds (append first, then attend), 1 <= T <= 32, over the
+        codes and the tail (csrc/msq_kv_packed_multi.hip).  q [B, Hq, T, D] in the cache dtype; with causal, query t sees the positions
+        <= len - T + t; bias float32 (may hold -inf) [B, len] (one row for every t) or [B, T, len], or None; returns [B, T, Hq, D] in
+        out_dtype (the q dtype or float32).  A row whose every position is masked gives zeros."""
+        if q.ndim != 4 or q.shape[0] != self.B or q.shape[3] != self.D or q.dtype != self.dtype:
+            raise MsqError("PackedKV.attend_multi: expected q [%d, Hq, T, %d] of %s" % (self.B, self.D, self.dtype))
+        Hq, T = int(q.shape[1]), int(q.shape[2])
+        if not 1 <= T <= MAX_QUERY_TOKENS:
+            raise MsqError("PackedKV.attend_multi: 1 .. %d query tokens, not %d" % (MAX_QUERY_TOKENS, T))
+        if T > self.len:
+            raise MsqError("PackedKV.attend_multi: %d query tokens but the cache holds %d (append first: the query tokens are the cache's last T)"
+                           % (T, self.len))
+        out_dtype = q.dtype if out_dtype is None else out_dtype
+        if out_dtype not in (q.dtype, torch.float32):
+            raise MsqError("PackedKV.attend_multi: out_dtype must be the q dtype or float32")
+        stride_t = 0
+        if bias is not None:
+            if tuple(bias.shape) == (self.B, T, self.len):
+                stride_t = self.len
+            elif tuple(bias.shape) != (self.B, self.len):
+                raise MsqError("PackedKV.attend_multi: bias must be [%d, %d] or [%d, %d, %d]" % (self.B, self.len, self.B, T, self.len))
+        _need_cuda(q, bias)
+        if self._capturing():
+            raise MsqError("PackedKV.attend_multi runs on host lengths and cannot be captured")
+        q = q.contiguous()
+        if q.data_ptr() % 16:
+            q = q.clone()
+        if bias is not None:
+            bias = bias.to(torch.float32).contiguous()
+        scaling = float(self.D) ** -0.5 if scaling is None else float(scaling)
+        need = lib().msq_kv_mx_attn_multi_workspace_bytes(self.B, Hq, self.Hkv, self.D, T, self.packed_len, self.tail_len)
+        if need < 0:
+            check(int(need), "msq_kv_mx_attn_multi_workspace_bytes")
+        ws = self._ws_multi
+        if ws is None or ws.numel() < need:
+            ws = self._ws_multi = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+        out = torch.empty(self.B, T, Hq, self.D, dtype=out_dtype, device=self.device)
+        p = self.planes
+        check(lib().msq_kv_mx_attn_multi(ptr(q), _DT[q.dtype], ptr(p["k_codes"]), ptr(p["k_scales"]), ptr(p["v_codes"]), ptr(p["v_scales"]),
+                                         self.packed_len, self.capacity, ptr(self.k_tail), ptr(self.v_tail), self.tail_len, self.gap,
+                                         ptr(bias), stride_t, int(bool(causal)), ptr(out), _DT[out_dtype], self.B, Hq, self.Hkv, self.D, T,
+                                         self.fmt_id, scaling, ptr(ws), ws.numel(), current_stream(self.device)), "msq_kv_mx_attn_multi")
+        return out
+
     @property
     def bits_per_element(self):
         """of the packed part: code bits + one scale byte per 32 elements"""
@@ -373,6 +453,12 @@ class StaticPackedKV(PackedKV):
         self.packed_len, self.tail_len = packed_len, tail_len
         self._write_state(clear_status=True)
 
+    def crop(self, n):
+        """PackedKV.crop, then the device state takes the mirror's lengths (one host-to-device copy).  n is counted on the MIRROR: after graph
+        replays call advance_host(steps) or sync() first, or the state is overwritten with lengths that are behind the device's."""
+        super().crop(n)
+        self._write_state()
+
     def sync(self):
         """read the device state back (one copy): the mirror takes its lengths; a status bit raises MsqError (set_lengths clears it)"""
         packed_len, tail_len, status, _ = self._read_state()
@@ -451,6 +537,7 @@ def _make_layer_class():
             self.elem_format, self.gap, self.capacity, self.max_len = elem_format, gap, capacity, max_len
             self.packed = None
             self.fused = False
+            self.fused_max_q = 1                                 # use_packed_attention(max_query_tokens=...): query lengths up to this are fused
 
         def lazy_initialization(self, key_states, value_states=None):
             _need_cuda(key_states)
@@ -467,9 +554,19 @@ def _make_layer_class():
             if not self.is_initialized:
                 self.lazy_initialization(key_states, value_states)
             self.packed.append(key_states, value_states)
-            if self.fused and key_states.shape[2] == 1:
+            if self.fused and 1 <= key_states.shape[2] <= self.fused_max_q:
                 return key_states, value_states
             return self.packed.dequantize()
+
+        def crop(self, max_length):
+            """keep the first max_length tokens (negative: drop that many from the end), as transformers' DynamicLayer.crop"""
+            if self.packed is None:
+                return
+            if max_length < 0:
+                max_length = self.packed.len - abs(max_length)
+            if self.packed.len <= max_length:
+                return
+            self.packed.crop(max(int(max_length), 0))
 
         def get_seq_length(self):
             return self.packed.len if self.packed is not None else 0
@@ -506,10 +603,29 @@ def PackedMXKVCache(num_layers, elem_format="fp8_e4m3", gap=32, capacity=256, ma
     return Cache(layers=[layer_cls(elem_format, gap, capacity, max_len) for _ in range(num_layers)])
 
 
+def _mask_bias(am, B):
+    """an sdpa mask slice (bool: True = attend, or additive) -> a float32 bias over B sequences"""
+    if am.dtype == torch.bool:
+        bias = torch.zeros(am.shape, dtype=torch.float32, device=am.device).masked_fill_(~am, float("-inf"))
+    else:
+        bias = am.to(torch.float32)
+    if bias.shape[0] != B:
+        bias = bias.expand(B, *bias.shape[1:])
+    return bias
+
+
 def _packed_attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None, **kwargs):
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
     layer = getattr(module, "_msq_packed_layer", None)
-    if layer is None or layer.packed is None or query.shape[2] != 1:
+    T = query.shape[2]
+    if layer is not None and layer.packed is not None and 2 <= T <= getattr(layer, "fused_max_q", 1):
+        bias = None                                              # no mask: the T tokens are the cache's last T, causal among themselves
+        if attention_mask is not None:
+            if attention_mask.ndim != 4 or attention_mask.shape[1] != 1 or attention_mask.shape[2] != T:
+                raise MsqError("msq_packed_kv: expected a [B, 1, %d, S] attention mask at query length %d" % (T, T))
+            bias = _mask_bias(attention_mask[:, 0], query.shape[0])
+        return layer.packed.attend_multi(query, bias, causal=bias is None, scaling=scaling), None      # [B, T, Hq, D]
+    if layer is None or layer.packed is None or T != 1:
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
     bias = None
     if attention_mask is not None:
@@ -529,10 +645,15 @@ def _packed_attention_forward(module, query, key, value, attention_mask, dropout
     return out.unsqueeze(1), None                                # [B, 1, Hq, D], the layout the attention interface returns
 
 
-def use_packed_attention(model, cache):
+def use_packed_attention(model, cache, max_query_tokens=1):
     """Decode steps of `model` attend over the codes of `cache` (a PackedMXKVCache): registers the attention function "msq_packed_kv",
     ties every attention module to its cache layer (the registered function is not handed past_key_values: the module attribute is the
-    link) and selects the function in the model's config.  Query lengths above 1 go to sdpa on the dequantised tensors."""
+    link) and selects the function in the model's config.  Query lengths 2 .. max_query_tokens (at most 32) go to attend_multi (a
+    [B, 1, T, S] mask becomes its [B, T, S] bias, no mask means causal); longer ones -- with the default of 1, every length above 1 -- go
+    to sdpa on the dequantised tensors."""
+    max_query_tokens = int(max_query_tokens)
+    if not 1 <= max_query_tokens <= MAX_QUERY_TOKENS:
+        raise MsqError("use_packed_attention: max_query_tokens must be 1 .. %d" % MAX_QUERY_TOKENS)
     from transformers import AttentionInterface
     from transformers.masking_utils import AttentionMaskInterface, sdpa_mask
     AttentionInterface.register(ATTENTION_NAME, _packed_attention_forward)
@@ -546,6 +667,7 @@ def use_packed_attention(model, cache):
             raise MsqError("use_packed_attention: the cache has no packed layer %d" % idx)
         m._msq_packed_layer = cache.layers[idx]
         cache.layers[idx].fused = True
+        cache.layers[idx].fused_max_q = max_query_tokens
         tied += 1
     if not tied:
         raise MsqError("use_packed_attention: no attention module (layer_idx + q_proj / k_proj) found in the model")
