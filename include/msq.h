@@ -66,7 +66,8 @@ extern "C" {
 /* status bits written to *status_flag by the outlier kernels */
 #define MSQ_STATUS_NAN 1 /* one of the reference's NaN asserts (utils/quant.py:225-250) would fire */
 #define MSQ_STATUS_INEXACT 2 /* pack: a value is not exactly code * 2^scale (never silently wrong) */
-#define MSQ_STATUS_OVERFLOW 8 /* msq_kv_mx_append_dev: the packed cache was full (or its state was not a valid one); the token was dropped */
+#define MSQ_STATUS_OVERFLOW 8 /* msq_kv_mx_append_dev / _seq: the packed cache (_seq: the slot) was full (or its state was not a valid one); the token was dropped */
+#define MSQ_KV_SLOT_IDLE 1 /* msq_kv_mx_append_seq / msq_kv_mx_attn_decode_seq: bit 0 of a state row's flags word: the slot takes no token and attends to nothing */
 #define MSQ_STATUS_TIMEOUT 4 /* msq_gptq_block: a workgroup gave up waiting at the grid barrier (CUs held by another stream or process): the result is invalid */
 
 /* GEMM-ready plane kinds (what the fused kernel converts in-register with the CDNA4
@@ -531,6 +532,27 @@ int msq_kv_group_quant(const void* in, void* out, int dtype, int64_t B, int64_t 
  *                     then the tail); bias_stride >= S_cap + tail_cap; entries at or beyond the length are never read.  Lengths found
  *                     outside 0 .. S_cap / 0 .. tail_cap are cut to them.
  *
+ * Lengths per sequence: the B sequences of a layer are SLOTS with lengths of their own, so a ragged batch needs no left
+ * padding and a slot can be emptied and refilled (host writes of its state row, between launches) while the others go on, under one captured
+ * step.  The planes and the tail are those of the forms above ([B, H, S_cap, ..], [B, H, tail_cap, D]); slot b owns index b of the first axis.
+ *   state             int32[B][4] in device memory, 16-byte aligned, one row per slot: {packed_len, tail_len, status, flags}.  flags bit 0 =
+ *                     MSQ_KV_SLOT_IDLE.  A row is read by the blocks that work for its slot and written only by the advance kernel (and by
+ *                     the host between launches).  Every block cuts what it finds to the planes and the tail it was given (the rule of the
+ *                     _dev entries, per slot): a bad row cannot make a block read or write outside its slot.
+ *   msq_kv_mx_append_seq    msq_kv_mx_append_dev with the rule applied to every slot's own row: a slot whose tail is full flushes it to its own
+ *                     packed_len, the others do not; a full slot (or one with an invalid row) has none of its bytes or lengths changed and
+ *                     gets MSQ_STATUS_OVERFLOW in its OWN status word while the others advance; MSQ_STATUS_NAN of a flush goes to the
+ *                     flushing slot's status word; an idle slot writes nothing, keeps its lengths and raises no status.  Four launches
+ *                     whose grids depend on (B, H, D, tail_cap) only -- the slot is the grids' y axis (B <= 65535), so a block serves one
+ *                     slot and reads one row; the last launch moves the lengths with one lane per slot.
+ *   msq_kv_mx_attn_decode_seq   msq_kv_mx_attn_decode_dev with sequence b's lengths read from row b: grid (max_splits, Hkv, B) of
+ *                     msq_kv_mx_attn_plan_cap, every block derives the plan of ITS slot's packed_len and returns when its split does not
+ *                     exist; the partials of a (sequence, query head) lie max_splits apart in the workspace (its size is plan_cap's) and
+ *                     are combined over the slot's live splits in ascending order, so row b equals msq_kv_mx_attn_decode's output for
+ *                     that sequence alone, bit for bit.  An empty or idle slot gives zeros.  bias [B, bias_stride] f32 or NULL,
+ *                     bias_stride >= S_cap + tail_cap, indexed by the absolute token position: a ragged batch needs no padding bias.
+ * Both make the argument checks of the _dev entries and return MSQ_ERR_* before any launch.
+ *
  * More than one query token: causal attention of the LAST T tokens the cache holds over the codes, on the matrix cores.
  *   msq_kv_mx_attn_multi    out[b, t, hq, :] = softmax(scaling q[b, hq, t, :] K^T + bias + causal) V over the packed tokens 0 .. S_packed and
  *                     then the tail, as msq_kv_mx_attn_decode.  q [B, Hq, T, D] f16 / bf16 (the dtype of the tail), 1 <= T <= 32,
@@ -544,7 +566,7 @@ int msq_kv_group_quant(const void* in, void* out, int dtype, int64_t B, int64_t 
  *                     atomics: equal inputs give equal bits, and a row's bits do not depend on the rows it is computed with.
  *   msq_kv_mx_attn_multi_workspace_bytes   B Hq T n_splits (D + 2) floats, or a negative MSQ_ERR_*.
  * Not built: paged / block-table caches, prefill attention over the codes (more than 32 query tokens), MicroScopiQ outlier caches, a
- * device-length (_dev) form of msq_kv_mx_attn_multi and a device-side multi-token append.
+ * device-length (_dev / _seq) form of msq_kv_mx_attn_multi and a device-side multi-token append.
  * ------------------------------------------------------------------------- */
 int msq_kv_mx_pack(const void* in, int dtype, void* codes, void* scales, int64_t B, int64_t H, int64_t T, int64_t D, int64_t S_cap,
                    int64_t pos, int elem_fmt, int along_tokens, int* status_flag, void* stream);
@@ -565,6 +587,13 @@ int msq_kv_mx_attn_decode_dev(const void* q, int q_dtype, const void* k_codes, c
                               int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_cap, const int* state, const float* bias,
                               int64_t bias_stride, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt, float scaling,
                               void* workspace, int64_t workspace_bytes, void* stream);
+int msq_kv_mx_append_seq(const void* k_new, const void* v_new, int dtype, void* k_codes, void* k_scales, void* v_codes, void* v_scales,
+                         int64_t S_cap, void* k_tail, void* v_tail, int64_t tail_cap, int* state /* [B][4] */, int64_t B, int64_t H, int64_t D,
+                         int elem_fmt, void* stream);
+int msq_kv_mx_attn_decode_seq(const void* q, int q_dtype, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                              int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_cap, const int* state /* [B][4] */,
+                              const float* bias, int64_t bias_stride, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt,
+                              float scaling, void* workspace, int64_t workspace_bytes, void* stream);
 int64_t msq_kv_mx_attn_multi_workspace_bytes(int64_t B, int Hq, int Hkv, int D, int T, int64_t S_packed, int64_t tail_len);
 int msq_kv_mx_attn_multi(const void* q, int q_dtype, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
                          int64_t S_packed, int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_len, int64_t tail_cap,

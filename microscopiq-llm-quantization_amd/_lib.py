@@ -58,6 +58,9 @@ _SIGS = {
     "msq_kv_mx_attn_plan_cap": (C.c_int, [_i64, _i32, _i32, _i32, _i64, _i64, C.POINTER(_i32), C.POINTER(_i64)]),
     "msq_kv_mx_attn_decode_dev": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _i32,
                                             _i32, _f32, _vp, _i64, _vp]),
+    "msq_kv_mx_append_seq": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "msq_kv_mx_attn_decode_seq": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _i32,
+                                            _i32, _f32, _vp, _i64, _vp]),
     "msq_kv_mx_attn_multi_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i64, _i64]),
     "msq_kv_mx_attn_multi": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _i32, _i64, _i32,
                                        _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp]),

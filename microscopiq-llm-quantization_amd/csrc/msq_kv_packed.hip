@@ -21,8 +21,14 @@
 // Lengths on the device: msq_kv_mx_append_dev / msq_kv_mx_attn_decode_dev read {packed_len, tail_len} from an int32[4] state
 // in device memory instead of taking them as launch arguments, with grids fixed by the capacity, so that a decode step can be captured in a
 // HIP graph.  They are further instantiations of the kernels below (template switches DEVPOS / DEV): the host-length forms are unchanged.
+//
+// Lengths per sequence: msq_kv_mx_append_seq / msq_kv_mx_attn_decode_seq take state = int32[B][4], one row
+// {packed_len, tail_len, status, flags} per slot, so the sequences of a batch differ in length and a slot can be emptied and refilled between
+// replays of one captured step.  A third template switch (SEQ) beside DEVPOS / DEV: the slot sits on a grid axis of its own in every kernel, so
+// a block works for one slot and its state read stays wave-uniform; the host-length and the shared-row forms are unchanged.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/msq.h"
 #include "msq_device.h"
@@ -87,8 +93,10 @@ MSQ_D void mx_block32(const float (&a)[32], uint32_t (&cw)[FP4 ? 4 : 8], int& sb
 // and changed only by k_kvp_advance, a launch of its own behind every reader on the stream.
 // What a single-token append does in the state it finds: 0 nothing (the cache is full, or the state is not one this library wrote),
 // 1 the token goes to tail slot `slot`, 2 the full tail is packed at token `pos` first and the token goes to slot 0.
+// UNIFORM = false (the advance of the per-sequence form, one lane per slot): `state` differs between the lanes, a per-lane read.
+template <bool UNIFORM = true>
 MSQ_D int append_step(const int* state, int64_t S_cap, int tail_cap, int& pos, int& slot) {
-    const int pl = __builtin_amdgcn_readfirstlane(state[0]), tl = __builtin_amdgcn_readfirstlane(state[1]);
+    const int pl = UNIFORM ? __builtin_amdgcn_readfirstlane(state[0]) : state[0], tl = UNIFORM ? __builtin_amdgcn_readfirstlane(state[1]) : state[1];
     pos = pl; slot = tl;
     if (pl < 0 || pl % 32 || pl > S_cap || tl < 0 || tl > tail_cap) return 0;
     if (tl < tail_cap) return 1;
@@ -96,17 +104,26 @@ MSQ_D int append_step(const int* state, int64_t S_cap, int tail_cap, int& pos, i
     slot = 0;
     return 2;
 }
+// SEQ: `row` is the state row of the ONE slot this block works for (the slot is a grid axis, so the read is wave-uniform
+// like the shared row's).  3: the slot is idle (flags bit 0): nothing is written, the lengths stay and no status is raised.
+MSQ_D int append_step_seq(const int* row, int64_t S_cap, int tail_cap, int& pos, int& slot) {
+    if (__builtin_amdgcn_readfirstlane(row[3]) & MSQ_KV_SLOT_IDLE) { pos = 0; slot = 0; return 3; }
+    return append_step(row, S_cap, tail_cap, pos, slot);
+}
 
 // ---- pack, K form: one lane per (b h, token group, channel), channel fastest: 32 strided reads, coalesced across the lanes
 // DEVPOS (both pack kernels): the flush of msq_kv_mx_append_dev.  `in` is the tail [B H, T = tail_cap, D]; the position comes from `state`, the
 // launch does nothing unless the tail is full and fits, and the status bits go to state[2].
-template <int DT, bool FP4, bool DEVPOS = false>
+// SEQ (with DEVPOS): the grid is (blocks of ONE slot, B); `total` counts one slot's lanes, blockIdx.y is the slot, `state` is [B][4] and the block
+// reads its slot's row: a slot whose tail is full flushes to its own packed_len and raises its own status word, the others return.
+template <int DT, bool FP4, bool DEVPOS = false, bool SEQ = false>
 __global__ void __launch_bounds__(256)
 k_kvp_pack_k(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t total, int64_t T, int D,
              int64_t S_cap, int64_t pos, int* status_flag, int* state) {
     if (DEVPOS) {
         int p, slot;
-        if (append_step(state, S_cap, (int)T, p, slot) != 2) return;
+        if (SEQ) state += 4 * (int64_t)blockIdx.y;
+        if ((SEQ ? append_step_seq(state, S_cap, (int)T, p, slot) : append_step(state, S_cap, (int)T, p, slot)) != 2) return;
         pos = p; status_flag = state + 2;
     }
     const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -114,7 +131,7 @@ k_kvp_pack_k(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* 
     const int64_t t = live ? t0 : 0;
     const int64_t ng = T / 32;
     const int d = (int)(t % D);
-    const int64_t tg = (t / D) % ng, bh = t / ((int64_t)D * ng);
+    const int64_t tg = (t / D) % ng, bh = t / ((int64_t)D * ng) + (SEQ ? (int64_t)blockIdx.y * (total / ((int64_t)D * ng)) : 0);
     float a[32];
 #pragma unroll
     for (int i = 0; i < 32; ++i) a[i] = ld_any<DT>(in, (bh * T + tg * 32 + i) * D + d);
@@ -142,17 +159,19 @@ k_kvp_pack_k(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* 
 }
 
 // ---- pack, V form: one lane per (b h, token, block of 32 channels): 16-byte reads and stores
-template <int DT, bool FP4, bool DEVPOS = false>
+template <int DT, bool FP4, bool DEVPOS = false, bool SEQ = false>
 __global__ void __launch_bounds__(256)
 k_kvp_pack_v(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t total, int64_t T, int D,
              int64_t S_cap, int64_t pos, int* status_flag, int* state) {
     if (DEVPOS) {
         int p, slot;
-        if (append_step(state, S_cap, (int)T, p, slot) != 2) return;
+        if (SEQ) state += 4 * (int64_t)blockIdx.y;
+        if ((SEQ ? append_step_seq(state, S_cap, (int)T, p, slot) : append_step(state, S_cap, (int)T, p, slot)) != 2) return;
         pos = p; status_flag = state + 2;
     }
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
+    if (SEQ) t += (int64_t)blockIdx.y * total;                      // total: the lanes of one slot
     const int nb = D / 32;
     const int blk = (int)(t % nb);
     const int64_t row = t / nb, bh = row / T, tok = row % T;
@@ -222,7 +241,7 @@ struct AttnArgs {
     int Hq, G, nsplit, gps, S_packed, tail_len, tail_cap;
     int64_t S_cap;
     float scaling;
-    const int* state; int bias_stride;            // the device-length form (DEV): lengths from state, bias rows of bias_stride floats
+    const int* state; int bias_stride;            // the device-length forms (DEV; SEQ: state is [B][4]): lengths from state, bias rows of bias_stride floats
 };
 
 // Token splits of the decode kernel: a function of the packed groups alone (not of the batch or the head count), so a sequence gives the same
@@ -245,6 +264,11 @@ MSQ_D void dev_lengths(const int* state, int64_t S_cap, int tail_cap, int& S_pac
     pl = pl < 0 ? 0 : (pl > S_cap ? (int)S_cap : pl);
     S_packed = pl & ~31;
     tail_len = tl < 0 ? 0 : (tl > tail_cap ? tail_cap : tl);
+}
+// SEQ: the lengths of the slot whose state row is `row`; an idle slot counts as empty (its output rows are zeros)
+MSQ_D void seq_lengths(const int* row, int64_t S_cap, int tail_cap, int& S_packed, int& tail_len) {
+    dev_lengths(row, S_cap, tail_cap, S_packed, tail_len);
+    if (__builtin_amdgcn_readfirstlane(row[3]) & MSQ_KV_SLOT_IDLE) { S_packed = 0; tail_len = 0; }
 }
 
 constexpr float LOG2E = 1.44269504088896340736f;
@@ -274,7 +298,9 @@ MSQ_D void softmax_fold(float (&sc)[NP][GMAX], float (&m)[GMAX], float (&l)[GMAX
 
 // DEV: the grid is (max_splits of the capacity, Hkv, B); every block reads the lengths from A.state, derives the plan a host-length launch at
 // those lengths gets and returns when its split does not exist, so the live blocks do what that launch's blocks do, bit for bit.
-template <int D, bool FP4, int GMAX, int QDT, bool DEV = false>
+// SEQ (with DEV): A.state is [B][4] and the block reads the row of ITS sequence, so the plan is per slot; the partials of a (sequence, query
+// head) are gridDim.x = max_splits apart in the workspace whatever the slot's live splits (rows of different live counts must not overlap).
+template <int D, bool FP4, int GMAX, int QDT, bool DEV = false, bool SEQ = false>
 __global__ void __launch_bounds__(256)
 k_kvp_attn_split(const AttnArgs A) {
     constexpr int LPT = D / 8, TP = 64 / LPT, NP = 32 / TP;          // lanes per token, tokens per pass of a wave, passes per group of 32
@@ -287,7 +313,8 @@ k_kvp_attn_split(const AttnArgs A) {
     const int64_t bh = (int64_t)b * Hkv + hk;
     int S_packed = A.S_packed, tail_len = A.tail_len, nsplit = A.nsplit, gps = A.gps;
     if (DEV) {
-        dev_lengths(A.state, A.S_cap, A.tail_cap, S_packed, tail_len);
+        if (SEQ) seq_lengths(A.state + 4 * (int64_t)b, A.S_cap, A.tail_cap, S_packed, tail_len);
+        else dev_lengths(A.state, A.S_cap, A.tail_cap, S_packed, tail_len);
         const AttnPlan pl = attn_split_plan(S_packed / 32);
         nsplit = pl.nsplit; gps = pl.gps;
         if (split >= nsplit) return;
@@ -474,7 +501,7 @@ k_kvp_attn_split(const AttnArgs A) {
         float num = 0.f, den = 0.f;
 #pragma unroll
         for (int w = 0; w < 4; ++w) { const float f = ex(red[w][g][D] - mm); num += red[w][g][d] * f; den += red[w][g][D + 1] * f; }
-        float* o = A.ws + ((((int64_t)b * A.Hq + hk * G + g) * nsplit) + split) * (D + 2);
+        float* o = A.ws + ((((int64_t)b * A.Hq + hk * G + g) * (SEQ ? (int)gridDim.x : nsplit)) + split) * (D + 2);
         o[d] = num;
         if (d == 0) { o[D] = mn; o[D + 1] = den; }
     }
@@ -482,17 +509,20 @@ k_kvp_attn_split(const AttnArgs A) {
 
 // the splits of one (sequence, query head) in ascending order; a row whose every position is masked gives zeros
 // DEV: the number of live splits comes from the state, as in k_kvp_attn_split
-template <int D, int ODT, bool DEV = false>
+// SEQ: the grid is (Hq, B), `nsplit` arrives as the row stride (max_splits) and the live count comes from the sequence's own state row
+template <int D, int ODT, bool DEV = false, bool SEQ = false>
 __global__ void __launch_bounds__(D)
 k_kvp_attn_combine(const float* __restrict__ ws, void* __restrict__ out, int nsplit, const int* state, int64_t S_cap) {
+    const int wstride = nsplit;
     if (DEV) {
         int S_packed, tail_len;
-        dev_lengths(state, S_cap, 0, S_packed, tail_len);
+        if (SEQ) seq_lengths(state + 4 * (int64_t)blockIdx.y, S_cap, 0, S_packed, tail_len);
+        else dev_lengths(state, S_cap, 0, S_packed, tail_len);
         nsplit = attn_split_plan(S_packed / 32).nsplit;
     }
     const int d = threadIdx.x;
-    const int64_t row = blockIdx.x;                                   // b * Hq + hq
-    const float* p = ws + row * nsplit * (D + 2);
+    const int64_t row = SEQ ? (int64_t)blockIdx.y * gridDim.x + blockIdx.x : (int64_t)blockIdx.x;       // b * Hq + hq
+    const float* p = ws + row * (SEQ ? wstride : nsplit) * (D + 2);
     float mn = neg_inf();
     for (int s = 0; s < nsplit; ++s) mn = __builtin_fmaxf(mn, p[s * (D + 2) + D]);
     const float mm = (mn == neg_inf()) ? 0.f : mn;
@@ -523,21 +553,43 @@ int attn_plan(int64_t B, int Hq, int Hkv, int D, int64_t S_packed, int64_t tail_
 }
 
 // ---- the single-token append of the device-length cache (msq_kv_mx_append_dev), after the flush: one lane per 16 bytes of the token
+// SEQ: the grid is (blocks of one slot, B) and `total` one slot's lanes, as in the pack kernels; an idle or full slot takes no token
+template <bool SEQ = false>
 __global__ void __launch_bounds__(256)
 k_kvp_tail_put(const uint4* __restrict__ k_new, const uint4* __restrict__ v_new, uint4* __restrict__ k_tail, uint4* __restrict__ v_tail, int64_t total,
                int dv, int64_t S_cap, int tail_cap, const int* state) {
     int pos, slot;
-    if (append_step(state, S_cap, tail_cap, pos, slot) == 0) return;
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (SEQ) {
+        state += 4 * (int64_t)blockIdx.y;
+        const int step = append_step_seq(state, S_cap, tail_cap, pos, slot);
+        if (step == 0 || step == 3) return;
+    } else if (append_step(state, S_cap, tail_cap, pos, slot) == 0) return;
+    int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
+    if (SEQ) t += (int64_t)blockIdx.y * total;
     const int64_t bh = t / dv, dst = (bh * tail_cap + slot) * dv + t % dv;       // k_new / v_new [B H, 1, D], the tail [B H, tail_cap, D]
     k_tail[dst] = k_new[t];
     v_tail[dst] = v_new[t];
 }
 
 // ... and the lengths: one lane, a launch of its own behind every kernel that read the old ones
+// SEQ: one lane per slot (a per-lane read of the slot's row, plain stores to it): a full slot or one with an invalid row gets
+// MSQ_STATUS_OVERFLOW in its OWN status word and keeps its lengths, an idle slot is left alone, the others move.  nslots: B (SEQ only).
+template <bool SEQ = false>
 __global__ void __launch_bounds__(64)
-k_kvp_advance(int* state, int64_t S_cap, int tail_cap) {
+k_kvp_advance(int* state, int64_t S_cap, int tail_cap, int nslots) {
+    if (SEQ) {
+        const int b = blockIdx.x * 64 + threadIdx.x;
+        if (b >= nslots) return;
+        int* row = state + 4 * (int64_t)b;
+        if (row[3] & MSQ_KV_SLOT_IDLE) return;
+        int pos, slot;
+        const int step = append_step<false>(row, S_cap, tail_cap, pos, slot);
+        if (step == 0) { row[2] = row[2] | MSQ_STATUS_OVERFLOW; return; }
+        if (step == 2) row[0] = pos + tail_cap;
+        row[1] = slot + 1;
+        return;
+    }
     if (threadIdx.x) return;
     int pos, slot;
     const int step = append_step(state, S_cap, tail_cap, pos, slot);
@@ -546,12 +598,12 @@ k_kvp_advance(int* state, int64_t S_cap, int tail_cap) {
     state[1] = slot + 1;
 }
 
-// the two launches of a decode call (DEV: the device-length form, grid_x = the capacity's max_splits)
-template <bool DEV>
+// the two launches of a decode call (DEV: the device-length form, grid_x = the capacity's max_splits; SEQ: a state row per sequence)
+template <bool DEV, bool SEQ = false>
 int attn_launch(const AttnArgs& A, int q_dtype, void* out, int out_dtype, int64_t B, int Hkv, int D, bool f4, int grid_x, hipStream_t st, const char* fail) {
     const dim3 grid((unsigned)grid_x, (unsigned)Hkv, (unsigned)B), blk(256);
     const int gm = A.G <= 1 ? 1 : (A.G <= 2 ? 2 : (A.G <= 4 ? 4 : 8));
-#define MSQ_KVA(DV, F4, GM, QD) hipLaunchKernelGGL((k_kvp_attn_split<DV, F4, GM, QD, DEV>), grid, blk, 0, st, A)
+#define MSQ_KVA(DV, F4, GM, QD) hipLaunchKernelGGL((k_kvp_attn_split<DV, F4, GM, QD, DEV, SEQ>), grid, blk, 0, st, A)
 #define MSQ_KVA_Q(DV, F4, GM) do { if (q_dtype == 1) MSQ_KVA(DV, F4, GM, 1); else MSQ_KVA(DV, F4, GM, 2); } while (0)
 #define MSQ_KVA_G(DV, F4) do { if (gm == 1) MSQ_KVA_Q(DV, F4, 1); else if (gm == 2) MSQ_KVA_Q(DV, F4, 2); else if (gm == 4) MSQ_KVA_Q(DV, F4, 4); else MSQ_KVA_Q(DV, F4, 8); } while (0)
 #define MSQ_KVA_F(DV) do { if (f4) MSQ_KVA_G(DV, true); else MSQ_KVA_G(DV, false); } while (0)
@@ -561,12 +613,90 @@ int attn_launch(const AttnArgs& A, int q_dtype, void* out, int out_dtype, int64_
 #undef MSQ_KVA_Q
 #undef MSQ_KVA
     if (hipGetLastError() != hipSuccess) return kvp_fail(MSQ_ERR_LAUNCH, fail);
-    const dim3 cgrid((unsigned)(B * A.Hq));
-#define MSQ_KVC1(DV, OD) hipLaunchKernelGGL((k_kvp_attn_combine<DV, OD, DEV>), cgrid, dim3(DV), 0, st, (const float*)A.ws, out, A.nsplit, A.state, A.S_cap)
+    const dim3 cgrid = SEQ ? dim3((unsigned)A.Hq, (unsigned)B) : dim3((unsigned)(B * A.Hq));
+#define MSQ_KVC1(DV, OD) hipLaunchKernelGGL((k_kvp_attn_combine<DV, OD, DEV, SEQ>), cgrid, dim3(DV), 0, st, (const float*)A.ws, out, SEQ ? grid_x : A.nsplit, A.state, A.S_cap)
 #define MSQ_KVC(DV) do { if (out_dtype == 0) MSQ_KVC1(DV, 0); else if (out_dtype == 1) MSQ_KVC1(DV, 1); else MSQ_KVC1(DV, 2); } while (0)
     if (D == 64) MSQ_KVC(64); else MSQ_KVC(128);
 #undef MSQ_KVC
 #undef MSQ_KVC1
+    return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, fail);
+}
+
+// "<entry>: <what>" as the message msq_last_error() returns: the shared-row (_dev) and the per-sequence (_seq) entries share their bodies
+int kvp_fail_in(int code, const char* who, const char* what) {
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return kvp_fail(code, msg);
+}
+
+// msq_kv_mx_attn_decode_dev (SEQ = false: state int32[4]) and msq_kv_mx_attn_decode_seq (SEQ = true: state int32[B][4]): the same checks, the
+// same grid of the split kernel
+template <bool SEQ>
+int attn_decode_state(const char* who, const void* q, int q_dtype, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                      int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_cap, const int* state, const float* bias,
+                      int64_t bias_stride, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt, float scaling,
+                      void* workspace, int64_t workspace_bytes, void* stream) {
+    int ms = 0;
+    int64_t need = 0;
+    const int rc = msq_kv_mx_attn_plan_cap(B, Hq, Hkv, D, S_cap, tail_cap, &ms, &need);
+    if (rc != MSQ_OK) return rc;
+    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "elem_fmt must be fp8_e4m3 or fp4_e2m1");
+    if (q_dtype != 1 && q_dtype != 2) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "q and the tail must be f16 (1) or bf16 (2)");
+    if (out_dtype != 0 && out_dtype != q_dtype) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "out must be float32 or the q dtype");
+    if (!state) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "null state");
+    if (bias && (bias_stride < S_cap + tail_cap || bias_stride > 0x7FFFFFFF))
+        return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "bias_stride must be at least S_cap + tail_cap");
+    if (!q || !out || !workspace || !k_tail || !v_tail) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "null buffer");
+    if (S_cap && (!k_codes || !k_scales || !v_codes || !v_scales)) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "null buffer (planes)");
+    if (workspace_bytes < need) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "workspace too small (msq_kv_mx_attn_plan_cap)");
+    if ((((uintptr_t)q | (uintptr_t)k_codes | (uintptr_t)k_scales | (uintptr_t)v_codes | (uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)workspace | (uintptr_t)state) & 15) != 0)
+        return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "buffers must be 16-byte aligned");
+    AttnArgs A;
+    A.q = q; A.kc = (const uint8_t*)k_codes; A.ks = (const uint8_t*)k_scales; A.vc = (const uint8_t*)v_codes; A.vs = (const uint8_t*)v_scales;
+    A.kt = k_tail; A.vt = v_tail; A.bias = bias; A.ws = (float*)workspace;
+    A.Hq = Hq; A.G = Hq / Hkv; A.nsplit = 0; A.gps = 0; A.S_packed = 0; A.tail_len = 0; A.tail_cap = (int)tail_cap;
+    A.S_cap = S_cap; A.scaling = scaling; A.state = state; A.bias_stride = (int)bias_stride;
+    char fail[96];
+    snprintf(fail, sizeof(fail), "%s: launch failed", who);
+    return attn_launch<true, SEQ>(A, q_dtype, out, out_dtype, B, Hkv, D, elem_fmt == MSQ_FMT_FP4_E2M1, ms, (hipStream_t)stream, fail);
+}
+
+// msq_kv_mx_append_dev (SEQ = false) and msq_kv_mx_append_seq (SEQ = true: the slot is the grids' y axis, the advance has one lane per slot)
+template <bool SEQ>
+int append_state(const char* who, const void* k_new, const void* v_new, int dtype, void* k_codes, void* k_scales, void* v_codes, void* v_scales,
+                 int64_t S_cap, void* k_tail, void* v_tail, int64_t tail_cap, int* state, int64_t B, int64_t H, int64_t D, int elem_fmt, void* stream) {
+    if (B <= 0 || H <= 0) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "sizes must be positive");
+    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "elem_fmt must be fp8_e4m3 or fp4_e2m1");
+    if (dtype != 1 && dtype != 2) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "the cache dtype must be f16 (1) or bf16 (2)");
+    if (D <= 0 || D % 32 || D > 256) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "head_dim must be a multiple of 32, at most 256");
+    if (S_cap <= 0 || S_cap % 32 || S_cap > (int64_t)1 << 30) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "S_cap must be a positive multiple of 32, at most 2^30");
+    if (tail_cap <= 0 || tail_cap % 32 || tail_cap > (int64_t)1 << 20) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "tail_cap must be a positive multiple of 32");
+    if (SEQ && B > 65535) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "at most 65535 slots (the slot is a grid axis)");
+    if (!state) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "null state");
+    if (!k_new || !v_new || !k_codes || !k_scales || !v_codes || !v_scales || !k_tail || !v_tail) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "null buffer");
+    if ((((uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_codes | (uintptr_t)v_codes | (uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)state) & 15) != 0)
+        return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "buffers must be 16-byte aligned");
+    // SEQ: the totals count ONE slot's lanes and the slot is blockIdx.y
+    const int64_t nb = SEQ ? 1 : B, ny = SEQ ? B : 1;
+    const int64_t tot_k = nb * H * (tail_cap / 32) * D, tot_v = nb * H * tail_cap * (D / 32), tot_p = nb * H * (D / 8);
+    if ((tot_k + 255) / 256 > 0x7FFFFFFF || (tot_v + 255) / 256 > 0x7FFFFFFF) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "tensor too large for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    const bool f4 = elem_fmt == MSQ_FMT_FP4_E2M1;
+    const dim3 blk(256), gk((unsigned)((tot_k + 255) / 256), (unsigned)ny), gv((unsigned)((tot_v + 255) / 256), (unsigned)ny), gp((unsigned)((tot_p + 255) / 256), (unsigned)ny);
+    char fail[96];
+    snprintf(fail, sizeof(fail), "%s: launch failed", who);
+    // four launches, every grid a function of (B, H, D, tail_cap) alone: the flush (K form, V form: no-ops unless the tail is full and fits), the
+    // token into its slot, and the one thread (SEQ: one lane per slot) that moves the lengths once every reader of the old ones is done
+#define MSQ_KVF(K, DTV, F4, G, TAIL, C, SC, TOT) hipLaunchKernelGGL((K<DTV, F4, true, SEQ>), G, blk, 0, st, (const void*)TAIL, (uint8_t*)C, (uint8_t*)SC, TOT, tail_cap, (int)D, S_cap, (int64_t)0, (int*)nullptr, state)
+#define MSQ_KVF_DT(K, F4, G, TAIL, C, SC, TOT) do { if (dtype == 1) MSQ_KVF(K, 1, F4, G, TAIL, C, SC, TOT); else MSQ_KVF(K, 2, F4, G, TAIL, C, SC, TOT); } while (0)
+    if (f4) { MSQ_KVF_DT(k_kvp_pack_k, true, gk, k_tail, k_codes, k_scales, tot_k); MSQ_KVF_DT(k_kvp_pack_v, true, gv, v_tail, v_codes, v_scales, tot_v); }
+    else { MSQ_KVF_DT(k_kvp_pack_k, false, gk, k_tail, k_codes, k_scales, tot_k); MSQ_KVF_DT(k_kvp_pack_v, false, gv, v_tail, v_codes, v_scales, tot_v); }
+#undef MSQ_KVF_DT
+#undef MSQ_KVF
+    if (hipGetLastError() != hipSuccess) return kvp_fail(MSQ_ERR_LAUNCH, fail);
+    hipLaunchKernelGGL(k_kvp_tail_put<SEQ>, gp, blk, 0, st, (const uint4*)k_new, (const uint4*)v_new, (uint4*)k_tail, (uint4*)v_tail, tot_p, (int)(D / 8), S_cap,
+                       (int)tail_cap, (const int*)state);
+    hipLaunchKernelGGL(k_kvp_advance<SEQ>, dim3(SEQ ? (unsigned)((B + 63) / 64) : 1u), dim3(64), 0, st, state, S_cap, (int)tail_cap, (int)B);
     return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, fail);
 }
 
@@ -688,60 +818,30 @@ int msq_kv_mx_attn_decode_dev(const void* q, int q_dtype, const void* k_codes, c
                               int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_cap, const int* state, const float* bias,
                               int64_t bias_stride, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt, float scaling,
                               void* workspace, int64_t workspace_bytes, void* stream) {
-    int ms = 0;
-    int64_t need = 0;
-    const int rc = msq_kv_mx_attn_plan_cap(B, Hq, Hkv, D, S_cap, tail_cap, &ms, &need);
-    if (rc != MSQ_OK) return rc;
-    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode_dev: elem_fmt must be fp8_e4m3 or fp4_e2m1");
-    if (q_dtype != 1 && q_dtype != 2) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode_dev: q and the tail must be f16 (1) or bf16 (2)");
-    if (out_dtype != 0 && out_dtype != q_dtype) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode_dev: out must be float32 or the q dtype");
-    if (!state) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: null state");
-    if (bias && (bias_stride < S_cap + tail_cap || bias_stride > 0x7FFFFFFF))
-        return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: bias_stride must be at least S_cap + tail_cap");
-    if (!q || !out || !workspace || !k_tail || !v_tail) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: null buffer");
-    if (S_cap && (!k_codes || !k_scales || !v_codes || !v_scales)) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: null buffer (planes)");
-    if (workspace_bytes < need) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: workspace too small (msq_kv_mx_attn_plan_cap)");
-    if ((((uintptr_t)q | (uintptr_t)k_codes | (uintptr_t)k_scales | (uintptr_t)v_codes | (uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)workspace | (uintptr_t)state) & 15) != 0)
-        return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode_dev: buffers must be 16-byte aligned");
-    AttnArgs A;
-    A.q = q; A.kc = (const uint8_t*)k_codes; A.ks = (const uint8_t*)k_scales; A.vc = (const uint8_t*)v_codes; A.vs = (const uint8_t*)v_scales;
-    A.kt = k_tail; A.vt = v_tail; A.bias = bias; A.ws = (float*)workspace;
-    A.Hq = Hq; A.G = Hq / Hkv; A.nsplit = 0; A.gps = 0; A.S_packed = 0; A.tail_len = 0; A.tail_cap = (int)tail_cap;
-    A.S_cap = S_cap; A.scaling = scaling; A.state = state; A.bias_stride = (int)bias_stride;
-    return attn_launch<true>(A, q_dtype, out, out_dtype, B, Hkv, D, elem_fmt == MSQ_FMT_FP4_E2M1, ms, (hipStream_t)stream, "msq_kv_mx_attn_decode_dev: launch failed");
+    return attn_decode_state<false>("msq_kv_mx_attn_decode_dev", q, q_dtype, k_codes, k_scales, v_codes, v_scales, S_cap, k_tail, v_tail, tail_cap, state, bias,
+                                    bias_stride, out, out_dtype, B, Hq, Hkv, D, elem_fmt, scaling, workspace, workspace_bytes, stream);
 }
 
 int msq_kv_mx_append_dev(const void* k_new, const void* v_new, int dtype, void* k_codes, void* k_scales, void* v_codes, void* v_scales,
                          int64_t S_cap, void* k_tail, void* v_tail, int64_t tail_cap, int* state, int64_t B, int64_t H, int64_t D, int elem_fmt,
                          void* stream) {
-    if (B <= 0 || H <= 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: sizes must be positive");
-    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_append_dev: elem_fmt must be fp8_e4m3 or fp4_e2m1");
-    if (dtype != 1 && dtype != 2) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_append_dev: the cache dtype must be f16 (1) or bf16 (2)");
-    if (D <= 0 || D % 32 || D > 256) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_append_dev: head_dim must be a multiple of 32, at most 256");
-    if (S_cap <= 0 || S_cap % 32 || S_cap > (int64_t)1 << 30) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: S_cap must be a positive multiple of 32, at most 2^30");
-    if (tail_cap <= 0 || tail_cap % 32 || tail_cap > (int64_t)1 << 20) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: tail_cap must be a positive multiple of 32");
-    if (!state) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: null state");
-    if (!k_new || !v_new || !k_codes || !k_scales || !v_codes || !v_scales || !k_tail || !v_tail) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: null buffer");
-    if ((((uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_codes | (uintptr_t)v_codes | (uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)state) & 15) != 0)
-        return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_append_dev: buffers must be 16-byte aligned");
-    const int64_t tot_k = B * H * (tail_cap / 32) * D, tot_v = B * H * tail_cap * (D / 32), tot_p = B * H * (D / 8);
-    if ((tot_k + 255) / 256 > 0x7FFFFFFF || (tot_v + 255) / 256 > 0x7FFFFFFF) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_append_dev: tensor too large for one launch");
-    hipStream_t st = (hipStream_t)stream;
-    const bool f4 = elem_fmt == MSQ_FMT_FP4_E2M1;
-    const dim3 blk(256), gk((unsigned)((tot_k + 255) / 256)), gv((unsigned)((tot_v + 255) / 256)), gp((unsigned)((tot_p + 255) / 256));
-    // four launches, every grid a function of (B, H, D, tail_cap) alone: the flush (K form, V form: no-ops unless the tail is full and fits), the
-    // token into its slot, and the one thread that moves the lengths once every reader of the old ones is done
-#define MSQ_KVF(K, DTV, F4, G, TAIL, C, SC, TOT) hipLaunchKernelGGL((K<DTV, F4, true>), G, blk, 0, st, (const void*)TAIL, (uint8_t*)C, (uint8_t*)SC, TOT, tail_cap, (int)D, S_cap, (int64_t)0, (int*)nullptr, state)
-#define MSQ_KVF_DT(K, F4, G, TAIL, C, SC, TOT) do { if (dtype == 1) MSQ_KVF(K, 1, F4, G, TAIL, C, SC, TOT); else MSQ_KVF(K, 2, F4, G, TAIL, C, SC, TOT); } while (0)
-    if (f4) { MSQ_KVF_DT(k_kvp_pack_k, true, gk, k_tail, k_codes, k_scales, tot_k); MSQ_KVF_DT(k_kvp_pack_v, true, gv, v_tail, v_codes, v_scales, tot_v); }
-    else { MSQ_KVF_DT(k_kvp_pack_k, false, gk, k_tail, k_codes, k_scales, tot_k); MSQ_KVF_DT(k_kvp_pack_v, false, gv, v_tail, v_codes, v_scales, tot_v); }
-#undef MSQ_KVF_DT
-#undef MSQ_KVF
-    if (hipGetLastError() != hipSuccess) return kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_append_dev: launch failed");
-    hipLaunchKernelGGL(k_kvp_tail_put, gp, blk, 0, st, (const uint4*)k_new, (const uint4*)v_new, (uint4*)k_tail, (uint4*)v_tail, tot_p, (int)(D / 8), S_cap,
-                       (int)tail_cap, (const int*)state);
-    hipLaunchKernelGGL(k_kvp_advance, dim3(1), dim3(64), 0, st, state, S_cap, (int)tail_cap);
-    return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_append_dev: launch failed");
+    return append_state<false>("msq_kv_mx_append_dev", k_new, v_new, dtype, k_codes, k_scales, v_codes, v_scales, S_cap, k_tail, v_tail, tail_cap, state, B, H, D,
+                               elem_fmt, stream);
+}
+
+int msq_kv_mx_attn_decode_seq(const void* q, int q_dtype, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                              int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_cap, const int* state, const float* bias,
+                              int64_t bias_stride, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D, int elem_fmt, float scaling,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+    return attn_decode_state<true>("msq_kv_mx_attn_decode_seq", q, q_dtype, k_codes, k_scales, v_codes, v_scales, S_cap, k_tail, v_tail, tail_cap, state, bias,
+                                   bias_stride, out, out_dtype, B, Hq, Hkv, D, elem_fmt, scaling, workspace, workspace_bytes, stream);
+}
+
+int msq_kv_mx_append_seq(const void* k_new, const void* v_new, int dtype, void* k_codes, void* k_scales, void* v_codes, void* v_scales,
+                         int64_t S_cap, void* k_tail, void* v_tail, int64_t tail_cap, int* state, int64_t B, int64_t H, int64_t D, int elem_fmt,
+                         void* stream) {
+    return append_state<true>("msq_kv_mx_append_seq", k_new, v_new, dtype, k_codes, k_scales, v_codes, v_scales, S_cap, k_tail, v_tail, tail_cap, state, B, H, D,
+                              elem_fmt, stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,8 @@ results are not always code x 2^e (parity table).
   StaticPackedKV      the same with a fixed capacity and the lengths in device memory: a decode step -- append(k, v), then
                       attend_dev(q) -- launches the same kernels with the same arguments at every length, so it can be captured in a HIP
                       graph and replayed; the host keeps a mirror of the lengths that every Python call advances without a device read
+  SlotPackedKV        StaticPackedKV with a state row PER SEQUENCE: B slots with lengths of their own, so a ragged batch needs
+                      no left padding, and a slot can be reset and prefilled again between replays of ONE captured step while the others go on
   PackedMXKVCache     a transformers Cache whose layers wrap PackedKV; update() returns dequantize(), so any attention works
   use_packed_attention registers the attention function "msq_packed_kv" and ties a model's attention modules to the cache's layers
 
@@ -19,9 +21,11 @@ Query lengths 2 .. 32: ``PackedKV.attend_multi`` is causal att
 the matrix cores (csrc/msq_kv_packed_multi.hip) -- a few draft tokens to verify, a short chunk of new tokens -- and ``PackedKV.crop`` takes
 rejected tokens back.  ``use_packed_attention(model, cache, max_query_tokens=T)`` routes those lengths to it.
 
-Not built: paged or block-table caches, prefill attention over the codes (more than 32 query tokens go to sdpa on the dequantised tensors),
-MicroScopiQ outlier caches, a device-length form of attend_multi and a device-side multi-token append (both run on the host mirror's lengths
-and cannot be captured), capture of a whole transformers model (its mask and position plumbing is not ours: PackedMXKVCache(max_len=...)
+Not built: paged or block-table caches (SlotPackedKV keeps planes [B, Hkv, S_cap, ..]: a slot reserves max_len tokens; per-sequence lengths
+are the prerequisite for paging, not paging), a transformers Cache over SlotPackedKV (transformers batches by left padding on one shared
+length), prefill attention over the codes (more than 32 query tokens go to sdpa on the dequantised tensors),
+MicroScopiQ outlier caches, a device-length or per-sequence form of attend_multi and a device-side multi-token append (both run on the host
+mirror's lengths and cannot be captured), capture of a whole transformers model (its mask and position plumbing is not ours: PackedMXKVCache(max_len=...)
 runs eagerly).  Every entry raises MsqError on CPU tensors: there is no CPU fallback."""
 import ctypes as C
 
@@ -36,6 +40,7 @@ GROUP = 32                                                       # the MX block:
 MAX_QUERY_TOKENS = 32                                            # of attend_multi (msq_kv_mx_attn_multi)
 ATTENTION_NAME = "msq_packed_kv"
 STATUS_NAN, STATUS_OVERFLOW = 1, 8                               # include/msq.h MSQ_STATUS_*
+SLOT_IDLE = 1                                                    # include/msq.h MSQ_KV_SLOT_IDLE: bit 0 of a state row's flags word
 
 
 def _fmt_id(elem_format):
@@ -363,6 +368,8 @@ class StaticPackedKV(PackedKV):
     ``advance_host(n)`` after n replayed steps, or ``sync()`` to read the state back (which also raises on a status bit).  A warm-up before
     capture moves the lengths like any other step: undo it with ``set_lengths``."""
 
+    _APPEND_ENTRY, _ATTN_ENTRY = "msq_kv_mx_append_dev", "msq_kv_mx_attn_decode_dev"      # SlotPackedKV: the _seq entries, the same arguments
+
     def __init__(self, B, Hkv, D, dtype, elem_format="fp8_e4m3", gap=32, max_len=256, device="cuda"):
         if gap <= 0 or gap % GROUP:
             raise MsqError("StaticPackedKV: gap must be a positive multiple of 32")
@@ -409,9 +416,9 @@ class StaticPackedKV(PackedKV):
                 raise MsqError("StaticPackedKV.append: k and v must be 16-byte aligned during capture")
             k, v = k.clone(), v.clone()
         p = self.planes
-        check(lib().msq_kv_mx_append_dev(ptr(k), ptr(v), _DT[self.dtype], ptr(p["k_codes"]), ptr(p["k_scales"]), ptr(p["v_codes"]),
-                                         ptr(p["v_scales"]), self.S_cap, ptr(self.k_tail), ptr(self.v_tail), self.gap, ptr(self.state),
-                                         self.B, self.Hkv, self.D, self.fmt_id, current_stream(self.device)), "msq_kv_mx_append_dev")
+        check(getattr(lib(), self._APPEND_ENTRY)(ptr(k), ptr(v), _DT[self.dtype], ptr(p["k_codes"]), ptr(p["k_scales"]), ptr(p["v_codes"]),
+                                                 ptr(p["v_scales"]), self.S_cap, ptr(self.k_tail), ptr(self.v_tail), self.gap, ptr(self.state),
+                                                 self.B, self.Hkv, self.D, self.fmt_id, current_stream(self.device)), self._APPEND_ENTRY)
 
     # ---- the cache ------------------------------------------------------------------------------------------------------------------
     def _after_steps(self, n):
@@ -515,12 +522,219 @@ class StaticPackedKV(PackedKV):
                                                 device=self.device)
         out = torch.empty(self.B, Hq, self.D, dtype=out_dtype, device=self.device)
         p = self.planes
-        check(lib().msq_kv_mx_attn_decode_dev(ptr(q), _DT[q.dtype], ptr(p["k_codes"]), ptr(p["k_scales"]), ptr(p["v_codes"]), ptr(p["v_scales"]),
-                                              self.S_cap, ptr(self.k_tail), ptr(self.v_tail), self.gap, ptr(self.state), ptr(bias),
-                                              bias.shape[1] if bias is not None else 0, ptr(out), _DT[out_dtype], self.B, Hq, self.Hkv,
-                                              self.D, self.fmt_id, scaling, ptr(ws), ws.numel(), current_stream(self.device)),
-              "msq_kv_mx_attn_decode_dev")
+        check(getattr(lib(), self._ATTN_ENTRY)(ptr(q), _DT[q.dtype], ptr(p["k_codes"]), ptr(p["k_scales"]), ptr(p["v_codes"]), ptr(p["v_scales"]),
+                                               self.S_cap, ptr(self.k_tail), ptr(self.v_tail), self.gap, ptr(self.state), ptr(bias),
+                                               bias.shape[1] if bias is not None else 0, ptr(out), _DT[out_dtype], self.B, Hq, self.Hkv,
+                                               self.D, self.fmt_id, scaling, ptr(ws), ws.numel(), current_stream(self.device)),
+              self._ATTN_ENTRY)
         return out
+
+
+class _SlotView(PackedKV):
+    """One slot of a SlotPackedKV as a PackedKV of batch 1 over that slot's (contiguous) slice of the planes and the tail: no storage of its
+    own, the lengths copied from the owner's mirror.  The host paths of PackedKV -- append by the timing rule, crop, dequantize -- run on it
+    unchanged, and msq_kv_mx_pack sees B = 1."""
+
+    def __init__(self, owner, slot):
+        self.B, self.Hkv, self.D, self.dtype = 1, owner.Hkv, owner.D, owner.dtype
+        self.elem_format, self.fmt_id, self.gap, self.device = owner.elem_format, owner.fmt_id, owner.gap, owner.device
+        self.capacity = owner.S_cap
+        self.packed_len, self.tail_len = owner._lens[slot]
+        self.planes = {n: t[slot:slot + 1] for n, t in owner.planes.items()}
+        self.k_tail, self.v_tail = owner.k_tail[slot:slot + 1], owner.v_tail[slot:slot + 1]
+        self._ws = self._ws_multi = None
+
+    def _reserve(self, need):
+        if need > self.capacity:
+            raise MsqError("SlotPackedKV: %d packed tokens exceed a slot's capacity of %d" % (need, self.capacity))
+
+
+_NO_SHARED_LENGTH = ("SlotPackedKV: attend, attend_multi and the transformers Cache wrapper are not offered on this class: both run on one "
+                     "shared host length, and transformers batches by left padding (use append / attend_dev, and prefill per slot)")
+
+
+class SlotPackedKV(StaticPackedKV):
+    """StaticPackedKV for a RAGGED batch: B slots of `max_len` tokens, ``state`` = int32[B, 4] with one row
+    {packed_len, tail_len, status, flags} per slot (flags bit 0: the slot is idle).
+
+    ``append(k, v)`` ([B, Hkv, 1, D]: one token for every slot that is not idle) and ``attend_dev(q)`` read every slot's own row inside their
+    kernels, with launches that depend on no length: the pair is captured once and replayed for ever, and between replays a slot is emptied
+    (``reset``), filled with a new prompt (``prefill``, the host path on that slot's slice of the planes), parked (``set_idle``) or cut
+    (``crop``) while the others go on.  ``lengths`` is the host's mirror per slot, advanced arithmetically (``advance_host`` after replays);
+    ``sync()`` reads the state back.  A slot that is full keeps its bytes and lengths and reports MSQ_STATUS_OVERFLOW in its own status word;
+    the others advance."""
+
+    _APPEND_ENTRY, _ATTN_ENTRY = "msq_kv_mx_append_seq", "msq_kv_mx_attn_decode_seq"
+    _VIEW = _SlotView                                            # overridden by the host test's stub
+
+    def __init__(self, B, Hkv, D, dtype, elem_format="fp8_e4m3", gap=32, max_len=256, device="cuda"):
+        self._lens = [(0, 0)] * int(B)                           # the mirror: (packed_len, tail_len) per slot
+        self._idle = [False] * int(B)
+        super().__init__(B, Hkv, D, dtype, elem_format, gap, max_len, device)
+
+    # ---- storage (overridden by the host test's stub) ------------------------------------------------------------------------------
+    def _alloc_state(self):
+        self.state = torch.zeros(self.B, 4, dtype=torch.int32, device=self.device)
+
+    def _write_row(self, slot, what):
+        """one host-to-device copy into slot's state row: "lengths" (words 0 .. 1), "flags" (word 3) or "all" (status cleared too)"""
+        p, t = self._lens[slot]
+        flags = SLOT_IDLE if self._idle[slot] else 0
+        if what == "lengths":
+            self.state[slot, :2].copy_(torch.tensor([p, t], dtype=torch.int32))
+        elif what == "flags":
+            self.state[slot, 3:].copy_(torch.tensor([flags], dtype=torch.int32))
+        else:
+            self.state[slot].copy_(torch.tensor([p, t, 0, flags], dtype=torch.int32))
+
+    # ---- the mirror ----------------------------------------------------------------------------------------------------------------
+    @property
+    def lengths(self):
+        """[(packed_len, tail_len)] per slot, from the host mirror"""
+        return list(self._lens)
+
+    @property
+    def len(self):
+        raise MsqError("SlotPackedKV has a length per slot: use lengths")
+
+    def __bool__(self):                                          # not __len__, which has no one answer here
+        return True
+
+    def _slot(self, slot):
+        slot = int(slot)
+        if not 0 <= slot < self.B:
+            raise MsqError("SlotPackedKV: slot must be 0 .. %d, not %d" % (self.B - 1, slot))
+        return slot
+
+    def _slot_after(self, slot, n):
+        """(lengths of the slot after n single-token steps, does it take all n): a slot holds S_cap packed tokens + a full tail and stays there"""
+        p, t = self._lens[slot]
+        fits = min(n, self.S_cap + self.gap - (p + t))
+        if fits > 0:
+            flushes = (t + fits - 1) // self.gap
+            p, t = p + flushes * self.gap, t + fits - flushes * self.gap
+        return (p, t), fits == n
+
+    def _steps(self, n, who):
+        live = [b for b in range(self.B) if not self._idle[b]]
+        after = {b: self._slot_after(b, n) for b in live}
+        if n > 0 and live and not any(ok for _, ok in after.values()):
+            raise MsqError("SlotPackedKV.%s: %d more token(s) overflow every live slot (capacity %d packed tokens; MSQ_STATUS_OVERFLOW on the "
+                           "device)" % (who, n, self.S_cap))
+        return after
+
+    def advance_host(self, n=1):
+        """apply n single-token steps to the mirror of every slot that is not idle (after n replays); a slot that fills up stops where the
+        device stops (its status word reports the overflow); refused when every live slot would overflow.  No device access."""
+        for b, (lens, _) in self._steps(int(n), "advance_host").items():
+            self._lens[b] = lens
+
+    def append(self, k, v):
+        """one token [B, Hkv, 1, D] for every slot that is not idle (an idle slot's row of k, v is ignored); can be captured.  Refused before
+        launching only if EVERY live slot would overflow; otherwise an overflowing slot's mirror stays and its device status reports it."""
+        self._check_kv(k, v)
+        if k.shape[2] != 1:
+            raise MsqError("SlotPackedKV.append takes one token per slot, [%d, %d, 1, %d]: more tokens go to one slot through prefill(slot, k, v)"
+                           % (self.B, self.Hkv, self.D))
+        after = self._steps(1, "append")
+        self._append_dev(k, v)
+        for b, (lens, _) in after.items():
+            self._lens[b] = lens
+
+    def _host_only(self, who):
+        if self._capturing():
+            raise MsqError("SlotPackedKV.%s writes a state row from the host and cannot be captured (call it between replays)" % who)
+
+    def prefill(self, slot, k, v):
+        """append T tokens k, v [1, Hkv, T, D] to ONE slot on the host path, by the timing rule of PackedKV.append (msq_kv_mx_pack on the
+        slot's slice of the planes with B = 1, the rest into the slot's tail rows), then one host-to-device copy of the slot's lengths.
+        The other slots' bytes and rows are not touched.  Refused during capture."""
+        slot = self._slot(slot)
+        self._host_only("prefill")
+        view = self._VIEW(self, slot)
+        view.append(k, v)
+        self._lens[slot] = (view.packed_len, view.tail_len)
+        self._write_row(slot, "lengths")
+
+    def reset(self, slot):
+        """slot := empty: lengths 0, status 0, not idle (one host-to-device copy); its bytes stay and are overwritten by what comes next"""
+        slot = self._slot(slot)
+        self._host_only("reset")
+        self._lens[slot], self._idle[slot] = (0, 0), False
+        self._write_row(slot, "all")
+
+    def set_idle(self, slot, idle=True):
+        """an idle slot takes no token, keeps its lengths and bytes, raises no status, and its rows of attend_dev are zeros"""
+        slot = self._slot(slot)
+        self._host_only("set_idle")
+        self._idle[slot] = bool(idle)
+        self._write_row(slot, "flags")
+
+    def set_lengths(self, slot, packed_len, tail_len):
+        """mirror and state row of one slot := (packed_len, tail_len), status cleared: restore after a warm-up, roll back"""
+        slot, packed_len, tail_len = self._slot(slot), int(packed_len), int(tail_len)
+        self._host_only("set_lengths")
+        if packed_len < 0 or packed_len % self.gap or packed_len > self.S_cap or not 0 <= tail_len <= self.gap:
+            raise MsqError("SlotPackedKV.set_lengths: packed_len must be a multiple of gap within the capacity, tail_len within the tail")
+        self._lens[slot] = (packed_len, tail_len)
+        self._write_row(slot, "all")
+
+    def crop(self, slot, n):
+        """PackedKV.crop on one slot (n counted on the MIRROR), then that slot's state row takes the lengths"""
+        slot = self._slot(slot)
+        self._host_only("crop")
+        view = self._VIEW(self, slot)
+        view.crop(n)
+        self._lens[slot] = (view.packed_len, view.tail_len)
+        self._write_row(slot, "lengths")
+
+    def dequantize(self, slot):
+        """one slot's K and V as [1, Hkv, len, D] in the cache dtype"""
+        return self._VIEW(self, self._slot(slot)).dequantize()
+
+    def sync(self, raise_on_status=True):
+        """read the state back (one copy): the mirror takes every slot's lengths and idle flag.  Returns the list of lengths; a status bit
+        raises MsqError naming the slot(s) and bit(s) -- or, with raise_on_status=False, returns (lengths, statuses) so that a server can
+        retire the one full slot (reset(slot) clears its status)."""
+        rows = self._read_state()
+        self._lens = [(int(r[0]), int(r[1])) for r in rows]
+        self._idle = [bool(int(r[3]) & SLOT_IDLE) for r in rows]
+        statuses = [int(r[2]) for r in rows]
+        if not raise_on_status:
+            return self.lengths, statuses
+        bad = []
+        for b, st in enumerate(statuses):
+            names = [n for bit, n in ((STATUS_OVERFLOW, "MSQ_STATUS_OVERFLOW"), (STATUS_NAN, "MSQ_STATUS_NAN")) if st & bit]
+            if st & ~(STATUS_OVERFLOW | STATUS_NAN):
+                names.append("status %d" % st)
+            if names:
+                bad.append("slot %d: %s" % (b, " | ".join(names)))
+        if bad:
+            raise MsqError("SlotPackedKV: " + "; ".join(bad) + " (overflow: an append found the slot full and dropped its token; nan: a packed "
+                           "block holds Inf / NaN; reset(slot) clears it)")
+        return self.lengths
+
+    def attend_dev(self, q, bias=None, scaling=None, out_dtype=None):
+        """row b = softmax(scaling q[b] K_b^T + bias[b]) V_b over slot b's OWN tokens (its lengths read from its state row by the kernels):
+        the bits PackedKV.attend gives for that sequence alone; zeros for an empty or idle slot.  bias [B, W] float32 with W >= S_cap + gap,
+        indexed by the absolute token position, or None: a ragged batch needs no padding bias.  Can be captured after one eager call."""
+        if bias is not None and (bias.ndim != 2 or bias.shape[0] != self.B or bias.shape[1] < self.S_cap + self.gap):
+            raise MsqError("SlotPackedKV.attend_dev: bias must be [%d, W] with W >= %d (S_cap + gap): the slots have no common length"
+                           % (self.B, self.S_cap + self.gap))
+        return super().attend_dev(q, bias, scaling, out_dtype)
+
+    # ---- not offered ---------------------------------------------------------------------------------------------------------------
+    def attend(self, *args, **kwargs):
+        raise MsqError(_NO_SHARED_LENGTH)
+
+    def attend_multi(self, *args, **kwargs):
+        raise MsqError(_NO_SHARED_LENGTH)
+
+    def update(self, *args, **kwargs):                           # the transformers cache-layer protocol
+        raise MsqError(_NO_SHARED_LENGTH)
+
+    def get_seq_length(self, *args, **kwargs):
+        raise MsqError(_NO_SHARED_LENGTH)
 
 
 def _make_layer_class():
