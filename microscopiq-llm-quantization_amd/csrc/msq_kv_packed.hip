@@ -26,25 +26,15 @@
 // {packed_len, tail_len, status, flags} per slot, so the sequences of a batch differ in length and a slot can be emptied and refilled between
 // replays of one captured step.  A third template switch (SEQ) beside DEVPOS / DEV: the slot sits on a grid axis of its own in every kernel, so
 // a block works for one slot and its state read stays wave-uniform; the host-length and the shared-row forms are unchanged.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include "../../include/msq.h"
-#include "msq_device.h"
+#include "msq_kv_packed_common.h"
 #include "msq_mx_pack_core.h"
 
 using namespace msq;
 
-extern "C" void msq_set_error_(const char* msg);      // msq_quant.hip: the message msq_last_error() returns
-
 namespace {
 
-typedef float v2f_t __attribute__((ext_vector_type(2)));
 typedef short v2s_t __attribute__((ext_vector_type(2)));
 
-MSQ_D float half_lo(uint32_t w, int dt) { return dt == 1 ? (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu)) : u2f(w << 16); }
-MSQ_D float half_hi(uint32_t w, int dt) { return dt == 1 ? (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)) : u2f(w & 0xFFFF0000u); }
 template <int DT> MSQ_D float ld_any(const void* p, int64_t i) {
     if (DT == 0) return reinterpret_cast<const float*>(p)[i];
     const uint16_t h = reinterpret_cast<const uint16_t*>(p)[i];
@@ -87,28 +77,6 @@ MSQ_D void mx_block32(const float (&a)[32], uint32_t (&cw)[FP4 ? 4 : 8], int& sb
             cw[p >> 1] = __builtin_bit_cast(uint32_t, cur);
         }
     }
-}
-
-// ---- device-held lengths: state = int32[4] {packed_len, tail_len, status, 0} of one layer, read by every block of a launch
-// and changed only by k_kvp_advance, a launch of its own behind every reader on the stream.
-// What a single-token append does in the state it finds: 0 nothing (the cache is full, or the state is not one this library wrote),
-// 1 the token goes to tail slot `slot`, 2 the full tail is packed at token `pos` first and the token goes to slot 0.
-// UNIFORM = false (the advance of the per-sequence form, one lane per slot): `state` differs between the lanes, a per-lane read.
-template <bool UNIFORM = true>
-MSQ_D int append_step(const int* state, int64_t S_cap, int tail_cap, int& pos, int& slot) {
-    const int pl = UNIFORM ? __builtin_amdgcn_readfirstlane(state[0]) : state[0], tl = UNIFORM ? __builtin_amdgcn_readfirstlane(state[1]) : state[1];
-    pos = pl; slot = tl;
-    if (pl < 0 || pl % 32 || pl > S_cap || tl < 0 || tl > tail_cap) return 0;
-    if (tl < tail_cap) return 1;
-    if ((int64_t)pl + tail_cap > S_cap) return 0;
-    slot = 0;
-    return 2;
-}
-// SEQ: `row` is the state row of the ONE slot this block works for (the slot is a grid axis, so the read is wave-uniform
-// like the shared row's).  3: the slot is idle (flags bit 0): nothing is written, the lengths stay and no status is raised.
-MSQ_D int append_step_seq(const int* row, int64_t S_cap, int tail_cap, int& pos, int& slot) {
-    if (__builtin_amdgcn_readfirstlane(row[3]) & MSQ_KV_SLOT_IDLE) { pos = 0; slot = 0; return 3; }
-    return append_step(row, S_cap, tail_cap, pos, slot);
 }
 
 // ---- pack, K form: one lane per (b h, token group, channel), channel fastest: 32 strided reads, coalesced across the lanes
@@ -205,9 +173,6 @@ k_kvp_pack_v(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* 
     if (status && status_flag) atomicOr(status_flag, status);
 }
 
-// value of a code pair: the scaled convert at scale 1, then the exact power of two (scale byte 255: the block held Inf / NaN)
-MSQ_D float apply_e8m0(float v, int sb) { return sb == 255 ? u2f(0x7FC00000u) : __builtin_ldexpf(v, sb - 127); }
-
 // ---- unpack: one lane per (b h, token, channel pair)
 template <int DT, bool FP4>
 __global__ void __launch_bounds__(256)
@@ -243,38 +208,6 @@ struct AttnArgs {
     float scaling;
     const int* state; int bias_stride;            // the device-length forms (DEV; SEQ: state is [B][4]): lengths from state, bias rows of bias_stride floats
 };
-
-// Token splits of the decode kernel: a function of the packed groups alone (not of the batch or the head count), so a sequence gives the same
-// bits whatever it is batched with.  A split is a whole number of groups of 32, a multiple of 4 groups (one per wave), at most 64 splits.
-// The one statement of the rule: the host plan and the device-length kernels both call it.
-struct AttnPlan { int nsplit, gps; };
-MSQ_HD AttnPlan attn_split_plan(int64_t ng) {
-    int64_t gps = (ng + 63) / 64;
-    gps = (gps + 3) / 4 * 4;
-    if (gps < 4) gps = 4;
-    AttnPlan p;
-    p.gps = (int)gps;
-    p.nsplit = ng ? (int)((ng + gps - 1) / gps) : 1;
-    return p;
-}
-
-// the lengths a device-length launch works with: whatever the state holds, cut to the planes and the tail it was given
-MSQ_D void dev_lengths(const int* state, int64_t S_cap, int tail_cap, int& S_packed, int& tail_len) {
-    int pl = __builtin_amdgcn_readfirstlane(state[0]), tl = __builtin_amdgcn_readfirstlane(state[1]);
-    pl = pl < 0 ? 0 : (pl > S_cap ? (int)S_cap : pl);
-    S_packed = pl & ~31;
-    tail_len = tl < 0 ? 0 : (tl > tail_cap ? tail_cap : tl);
-}
-// SEQ: the lengths of the slot whose state row is `row`; an idle slot counts as empty (its output rows are zeros)
-MSQ_D void seq_lengths(const int* row, int64_t S_cap, int tail_cap, int& S_packed, int& tail_len) {
-    dev_lengths(row, S_cap, tail_cap, S_packed, tail_len);
-    if (__builtin_amdgcn_readfirstlane(row[3]) & MSQ_KV_SLOT_IDLE) { S_packed = 0; tail_len = 0; }
-}
-
-constexpr float LOG2E = 1.44269504088896340736f;
-MSQ_D float ex(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }                 // e^x; e^-inf = 0
-MSQ_D float e8m0_f32(uint32_t sb) { return sb ? u2f(sb << 23) : u2f(0x00400000u); }   // 2^(sb - 127)
-MSQ_D float neg_inf() { return -__builtin_inff(); }
 
 // one group of NP tokens per lane: the scores sc[p][g] are in hand; fold them into the lane's running (m, l), rescale acc once, and leave the
 // probabilities in sc
@@ -338,10 +271,8 @@ k_kvp_attn_split(const AttnArgs A) {
         for (int j = 0; j < 8; ++j) acc[g][j] = 0.f;
     }
 
-    const int ngroups = S_packed / 32;
-    const int g0 = split * gps, g1 = (g0 + gps < ngroups) ? g0 + gps : ngroups;
-    const int npk = g1 > g0 ? g1 - g0 : 0;
-    const int ntc = (split == nsplit - 1) ? (tail_len + 31) / 32 : 0;      // the last split also takes the tail, 32 tokens at a time
+    int g0, npk, ntc;
+    split_range(split, nsplit, gps, S_packed, tail_len, g0, npk, ntc);
 
     for (int it = wv; it < npk + ntc; it += 4) {
         float sc[NP][GMAX];
@@ -507,51 +438,6 @@ k_kvp_attn_split(const AttnArgs A) {
     }
 }
 
-// the splits of one (sequence, query head) in ascending order; a row whose every position is masked gives zeros
-// DEV: the number of live splits comes from the state, as in k_kvp_attn_split
-// SEQ: the grid is (Hq, B), `nsplit` arrives as the row stride (max_splits) and the live count comes from the sequence's own state row
-template <int D, int ODT, bool DEV = false, bool SEQ = false>
-__global__ void __launch_bounds__(D)
-k_kvp_attn_combine(const float* __restrict__ ws, void* __restrict__ out, int nsplit, const int* state, int64_t S_cap) {
-    const int wstride = nsplit;
-    if (DEV) {
-        int S_packed, tail_len;
-        if (SEQ) seq_lengths(state + 4 * (int64_t)blockIdx.y, S_cap, 0, S_packed, tail_len);
-        else dev_lengths(state, S_cap, 0, S_packed, tail_len);
-        nsplit = attn_split_plan(S_packed / 32).nsplit;
-    }
-    const int d = threadIdx.x;
-    const int64_t row = SEQ ? (int64_t)blockIdx.y * gridDim.x + blockIdx.x : (int64_t)blockIdx.x;       // b * Hq + hq
-    const float* p = ws + row * (SEQ ? wstride : nsplit) * (D + 2);
-    float mn = neg_inf();
-    for (int s = 0; s < nsplit; ++s) mn = __builtin_fmaxf(mn, p[s * (D + 2) + D]);
-    const float mm = (mn == neg_inf()) ? 0.f : mn;
-    float num = 0.f, den = 0.f;
-    for (int s = 0; s < nsplit; ++s) {
-        const float f = ex(p[s * (D + 2) + D] - mm);
-        num += p[s * (D + 2) + d] * f; den += p[s * (D + 2) + D + 1] * f;
-    }
-    const float y = den > 0.f ? num / den : 0.f;
-    if (ODT == 0) reinterpret_cast<float*>(out)[row * D + d] = y;
-    else if (ODT == 1) reinterpret_cast<uint16_t*>(out)[row * D + d] = __builtin_bit_cast(uint16_t, (_Float16)y);
-    else reinterpret_cast<uint16_t*>(out)[row * D + d] = __builtin_bit_cast(uint16_t, (__bf16)y);
-}
-
-int kvp_fail(int code, const char* msg) { msq_set_error_(msg); return code; }
-
-int attn_plan(int64_t B, int Hq, int Hkv, int D, int64_t S_packed, int64_t tail_len, AttnPlan* p) {
-    if (B <= 0 || Hq <= 0 || Hkv <= 0 || S_packed < 0 || tail_len < 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: sizes must be positive");
-    if (Hq % Hkv) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: Hq must be a multiple of Hkv");
-    if (Hq / Hkv > 8) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn: at most 8 query heads per kv head");
-    if (D != 64 && D != 128) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn: head_dim must be 64 or 128");
-    if (S_packed % 32) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: S_packed must be a multiple of 32");
-    if (S_packed + tail_len == 0) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn: the cache is empty");
-    if (S_packed > (int64_t)1 << 30 || tail_len > (int64_t)1 << 20 || B > 65535 || Hkv > 65535)
-        return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn: sizes beyond the launch grid");
-    *p = attn_split_plan(S_packed / 32);
-    return MSQ_OK;
-}
-
 // ---- the single-token append of the device-length cache (msq_kv_mx_append_dev), after the flush: one lane per 16 bytes of the token
 // SEQ: the grid is (blocks of one slot, B) and `total` one slot's lanes, as in the pack kernels; an idle or full slot takes no token
 template <bool SEQ = false>
@@ -622,13 +508,6 @@ int attn_launch(const AttnArgs& A, int q_dtype, void* out, int out_dtype, int64_
     return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, fail);
 }
 
-// "<entry>: <what>" as the message msq_last_error() returns: the shared-row (_dev) and the per-sequence (_seq) entries share their bodies
-int kvp_fail_in(int code, const char* who, const char* what) {
-    char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return kvp_fail(code, msg);
-}
-
 // msq_kv_mx_attn_decode_dev (SEQ = false: state int32[4]) and msq_kv_mx_attn_decode_seq (SEQ = true: state int32[B][4]): the same checks, the
 // same grid of the split kernel
 template <bool SEQ>
@@ -640,20 +519,15 @@ int attn_decode_state(const char* who, const void* q, int q_dtype, const void* k
     int64_t need = 0;
     const int rc = msq_kv_mx_attn_plan_cap(B, Hq, Hkv, D, S_cap, tail_cap, &ms, &need);
     if (rc != MSQ_OK) return rc;
-    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "elem_fmt must be fp8_e4m3 or fp4_e2m1");
-    if (q_dtype != 1 && q_dtype != 2) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "q and the tail must be f16 (1) or bf16 (2)");
-    if (out_dtype != 0 && out_dtype != q_dtype) return kvp_fail_in(MSQ_ERR_UNSUPPORTED, who, "out must be float32 or the q dtype");
-    if (!state) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "null state");
-    if (bias && (bias_stride < S_cap + tail_cap || bias_stride > 0x7FFFFFFF))
-        return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "bias_stride must be at least S_cap + tail_cap");
-    if (!q || !out || !workspace || !k_tail || !v_tail) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "null buffer");
-    if (S_cap && (!k_codes || !k_scales || !v_codes || !v_scales)) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "null buffer (planes)");
-    if (workspace_bytes < need) return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "workspace too small (msq_kv_mx_attn_plan_cap)");
-    if ((((uintptr_t)q | (uintptr_t)k_codes | (uintptr_t)k_scales | (uintptr_t)v_codes | (uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)workspace | (uintptr_t)state) & 15) != 0)
-        return kvp_fail_in(MSQ_ERR_BAD_ARG, who, "buffers must be 16-byte aligned");
     AttnArgs A;
-    A.q = q; A.kc = (const uint8_t*)k_codes; A.ks = (const uint8_t*)k_scales; A.vc = (const uint8_t*)v_codes; A.vs = (const uint8_t*)v_scales;
-    A.kt = k_tail; A.vt = v_tail; A.bias = bias; A.ws = (float*)workspace;
+    set_attn_buffers(A, q, k_codes, k_scales, v_codes, v_scales, k_tail, v_tail, bias, workspace);
+    // the tail is read at whatever length the state holds: a null one is refused with q, out and the workspace
+    const char* own = !state ? "null state"
+                    : (bias && (bias_stride < S_cap + tail_cap || bias_stride > 0x7FFFFFFF)) ? "bias_stride must be at least S_cap + tail_cap"
+                    : (!k_tail || !v_tail) ? "null buffer" : nullptr;
+    const int bad = check_attn_common(who, A, out, state, elem_fmt, q_dtype, out_dtype, own, S_cap != 0, false, workspace_bytes, need,
+                                      "workspace too small (msq_kv_mx_attn_plan_cap)");
+    if (bad != MSQ_OK) return bad;
     A.Hq = Hq; A.G = Hq / Hkv; A.nsplit = 0; A.gps = 0; A.S_packed = 0; A.tail_len = 0; A.tail_cap = (int)tail_cap;
     A.S_cap = S_cap; A.scaling = scaling; A.state = state; A.bias_stride = (int)bias_stride;
     char fail[96];
@@ -779,21 +653,13 @@ int msq_kv_mx_attn_decode(const void* q, int q_dtype, const void* k_codes, const
     AttnPlan p;
     const int rc = attn_plan(B, Hq, Hkv, D, S_packed, tail_len, &p);
     if (rc != MSQ_OK) return rc;
-    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode: elem_fmt must be fp8_e4m3 or fp4_e2m1");
-    if (q_dtype != 1 && q_dtype != 2) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode: q and the tail must be f16 (1) or bf16 (2)");
-    if (out_dtype != 0 && out_dtype != q_dtype) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_decode: out must be float32 or the q dtype");
-    if (S_cap < 0 || S_cap % 32 || S_packed > S_cap) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: S_packed exceeds S_cap (a multiple of 32)");
-    if (tail_len > tail_cap) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: tail_len exceeds tail_cap");
-    if (!q || !out || !workspace) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: null buffer");
-    if (S_packed && (!k_codes || !k_scales || !v_codes || !v_scales)) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: null buffer (planes)");
-    if (tail_len && (!k_tail || !v_tail)) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: null buffer (tail)");
-    const int64_t need = B * Hq * (int64_t)p.nsplit * (D + 2) * (int64_t)sizeof(float);
-    if (workspace_bytes < need) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: workspace too small (msq_kv_mx_attn_workspace_bytes)");
-    if ((((uintptr_t)q | (uintptr_t)k_codes | (uintptr_t)k_scales | (uintptr_t)v_codes | (uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)workspace) & 15) != 0)
-        return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_decode: buffers must be 16-byte aligned");
     AttnArgs A;
-    A.q = q; A.kc = (const uint8_t*)k_codes; A.ks = (const uint8_t*)k_scales; A.vc = (const uint8_t*)v_codes; A.vs = (const uint8_t*)v_scales;
-    A.kt = k_tail; A.vt = v_tail; A.bias = bias; A.ws = (float*)workspace;
+    set_attn_buffers(A, q, k_codes, k_scales, v_codes, v_scales, k_tail, v_tail, bias, workspace);
+    const char* own = (S_cap < 0 || S_cap % 32 || S_packed > S_cap) ? "S_packed exceeds S_cap (a multiple of 32)"
+                    : tail_len > tail_cap ? "tail_len exceeds tail_cap" : nullptr;
+    const int bad = check_attn_common("msq_kv_mx_attn_decode", A, out, nullptr, elem_fmt, q_dtype, out_dtype, own, S_packed != 0, tail_len != 0, workspace_bytes,
+                                      B * Hq * (int64_t)p.nsplit * (D + 2) * (int64_t)sizeof(float), "workspace too small (msq_kv_mx_attn_workspace_bytes)");
+    if (bad != MSQ_OK) return bad;
     A.Hq = Hq; A.G = Hq / Hkv; A.nsplit = p.nsplit; A.gps = p.gps; A.S_packed = (int)S_packed; A.tail_len = (int)tail_len; A.tail_cap = (int)tail_cap;
     A.S_cap = S_cap; A.scaling = scaling; A.state = nullptr; A.bias_stride = 0;
     return attn_launch<false>(A, q_dtype, out, out_dtype, B, Hkv, D, elem_fmt == MSQ_FMT_FP4_E2M1, p.nsplit, (hipStream_t)stream, "msq_kv_mx_attn_decode: launch failed");

@@ -18,28 +18,16 @@
 // The waves merge through LDS in wave order, every split writes (acc[D], m, l) per row to the workspace, a second launch combines the splits
 // in ascending order.  No atomics, no flags, no block waits on another: equal inputs give equal bits, and a row's bits do not depend on the
 // rows it is computed with.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/msq.h"
-#include "msq_device.h"
+#include "msq_kv_packed_common.h"
 
 using namespace msq;
 
-extern "C" void msq_set_error_(const char* msg);      // msq_quant.hip: the message msq_last_error() returns
-
 namespace {
 
-typedef float v2f_t __attribute__((ext_vector_type(2)));
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 typedef short v4s_t __attribute__((ext_vector_type(4)));
 typedef __bf16 v8bf_t __attribute__((ext_vector_type(8)));
 typedef _Float16 v8h_t __attribute__((ext_vector_type(8)));
-
-constexpr float LOG2E = 1.44269504088896340736f;
-MSQ_D float ex(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }                 // e^x; e^-inf = 0
-MSQ_D float e8m0_f32(uint32_t sb) { return sb ? u2f(sb << 23) : u2f(0x00400000u); }   // 2^(sb - 127)
-MSQ_D float neg_inf() { return -__builtin_inff(); }
 
 // two float32 values that ARE bf16 values (low 16 bits zero) -> one packed word
 MSQ_D uint32_t pk_top(float lo, float hi) { return (f2u(lo) >> 16) | (f2u(hi) & 0xFFFF0000u); }
@@ -49,32 +37,10 @@ MSQ_D uint32_t pk_bf16(float lo, float hi) {
 MSQ_D uint32_t pk_f16(float lo, float hi) {
     return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)lo) | ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)hi) << 16);
 }
-MSQ_D float bf16_lo(uint32_t w) { return u2f(w << 16); }
-MSQ_D float bf16_hi(uint32_t w) { return u2f(w & 0xFFFF0000u); }
-MSQ_D float f16_lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu)); }
-MSQ_D float f16_hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
 
 template <bool F16> MSQ_D v4f_t mma(const uint4 a, const uint4 b, const v4f_t c) {
     if (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h_t, a), __builtin_bit_cast(v8h_t, b), c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf_t, a), __builtin_bit_cast(v8bf_t, b), c, 0, 0, 0);
-}
-
-// 8 codes of one token (8 consecutive channels) -> 4 float pairs at scale 1
-template <bool FP4> MSQ_D void cvt8(uint32_t c0, uint32_t c1, float sc, float (&f)[8]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        v2f_t v;
-        if (FP4) {
-            if (j == 0) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(c0, sc, 0);
-            else if (j == 1) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(c0, sc, 1);
-            else if (j == 2) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(c0, sc, 2);
-            else v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(c0, sc, 3);
-        } else {
-            if ((j & 1) == 0) v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(j < 2 ? c0 : c1, sc, false);
-            else v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(j < 2 ? c0 : c1, sc, true);
-        }
-        f[2 * j] = v[0]; f[2 * j + 1] = v[1];
-    }
 }
 
 // LDS traffic inside ONE wave (the V tile is wave-private): the stores are done and visible before the transposed reads, the reads are done
@@ -180,6 +146,9 @@ k_kvp_attn_multi_split(const MultiArgs A) {
     constexpr int LPT = D / 8, TP = 64 / LPT, NP = 32 / TP;           // the V tile's load pattern: lanes per token, tokens per pass, passes
     __shared__ __attribute__((aligned(16))) unsigned char smem[LOOP_BYTES > RED_BYTES ? LOOP_BYTES : RED_BYTES];
 
+    // the split's range (split_range below).  Declared first on purpose: where these three sit among the locals decides the order in which the
+    // compiler initialises m and l of the one-tile kernels, and here their instructions stay what they were
+    int g0, npk, ntc;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int c = lane & 15, h = lane >> 4;
     const int split = blockIdx.x, hk = blockIdx.y / A.ntiles, tile = blockIdx.y % A.ntiles, b = blockIdx.z;
@@ -236,10 +205,7 @@ k_kvp_attn_multi_split(const MultiArgs A) {
         for (int dc = 0; dc < DC; ++dc) O[n][dc] = v4f_t{0.f, 0.f, 0.f, 0.f};
     }
 
-    const int ngroups = S_packed / 32;
-    const int g0 = split * A.gps, g1 = (g0 + A.gps < ngroups) ? g0 + A.gps : ngroups;
-    const int npk = g1 > g0 ? g1 - g0 : 0;
-    const int ntc = (split == A.nsplit - 1) ? (tail_len + 31) / 32 : 0;    // the last split also takes the tail, 32 tokens at a time
+    split_range(split, A.nsplit, A.gps, S_packed, tail_len, g0, npk, ntc);
     unsigned char* vtile = smem + NQ * QIMG + wv * VTILE;
     const unsigned char* qfrag = smem + c * QSTR + h * 16;                // + n * 16 * QSTR + ks * 64: the B fragment of row n * 16 + c
     const int vc8 = lane % LPT, vts = lane / LPT;
@@ -388,37 +354,12 @@ k_kvp_attn_multi_split(const MultiArgs A) {
     }
 }
 
-// the splits of one (sequence, token, query head) in ascending order; a row whose every position is masked gives zeros
-template <int D, int ODT>
-__global__ void __launch_bounds__(D)
-k_kvp_attn_multi_combine(const float* __restrict__ ws, void* __restrict__ out, int nsplit) {
-    const int d = threadIdx.x;
-    const int64_t row = blockIdx.x;                                   // (b * T + t) * Hq + hq
-    const float* p = ws + row * nsplit * (D + 2);
-    float mn = neg_inf();
-    for (int s = 0; s < nsplit; ++s) mn = __builtin_fmaxf(mn, p[s * (D + 2) + D]);
-    const float mm = (mn == neg_inf()) ? 0.f : mn;
-    float num = 0.f, den = 0.f;
-    for (int s = 0; s < nsplit; ++s) {
-        const float f = ex(p[s * (D + 2) + D] - mm);
-        num += p[s * (D + 2) + d] * f; den += p[s * (D + 2) + D + 1] * f;
-    }
-    const float y = den > 0.f ? num / den : 0.f;
-    if (ODT == 0) reinterpret_cast<float*>(out)[row * D + d] = y;
-    else if (ODT == 1) reinterpret_cast<uint16_t*>(out)[row * D + d] = __builtin_bit_cast(uint16_t, (_Float16)y);
-    else reinterpret_cast<uint16_t*>(out)[row * D + d] = __builtin_bit_cast(uint16_t, (__bf16)y);
-}
-
-int kvm_fail(int code, const char* msg) { msq_set_error_(msg); return code; }
-
-// the checks of the sizes + the plan (msq_kv_mx_attn_plan: the single-token entry's, a function of S_packed alone)
-int multi_plan(int64_t B, int Hq, int Hkv, int D, int T, int64_t S_packed, int64_t tail_len, int* nsplit, int* gps) {
-    if (T < 1 || T > 32) return kvm_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: T must be 1 .. 32");
-    int st = 0;
-    const int rc = msq_kv_mx_attn_plan(B, Hq, Hkv, D, S_packed, tail_len, nsplit, &st, nullptr);
+// the checks of the sizes + the plan (the single-token entry's, a function of S_packed alone)
+int multi_plan(int64_t B, int Hq, int Hkv, int D, int T, int64_t S_packed, int64_t tail_len, AttnPlan* p) {
+    if (T < 1 || T > 32) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: T must be 1 .. 32");
+    const int rc = attn_plan(B, Hq, Hkv, D, S_packed, tail_len, p);
     if (rc != MSQ_OK) return rc;
-    if (T > S_packed + tail_len) return kvm_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: T exceeds the cached length (the query tokens are the cache's last T)");
-    if (gps) *gps = st / 32;
+    if (T > S_packed + tail_len) return kvp_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: T exceeds the cached length (the query tokens are the cache's last T)");
     return MSQ_OK;
 }
 
@@ -427,42 +368,35 @@ int multi_plan(int64_t B, int Hq, int Hkv, int D, int T, int64_t S_packed, int64
 extern "C" {
 
 int64_t msq_kv_mx_attn_multi_workspace_bytes(int64_t B, int Hq, int Hkv, int D, int T, int64_t S_packed, int64_t tail_len) {
-    int ns = 0;
-    const int rc = multi_plan(B, Hq, Hkv, D, T, S_packed, tail_len, &ns, nullptr);
-    return rc != MSQ_OK ? (int64_t)rc : B * Hq * (int64_t)T * ns * (D + 2) * (int64_t)sizeof(float);
+    AttnPlan p;
+    const int rc = multi_plan(B, Hq, Hkv, D, T, S_packed, tail_len, &p);
+    return rc != MSQ_OK ? (int64_t)rc : B * Hq * (int64_t)T * p.nsplit * (D + 2) * (int64_t)sizeof(float);
 }
 
 int msq_kv_mx_attn_multi(const void* q, int q_dtype, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
                          int64_t S_packed, int64_t S_cap, const void* k_tail, const void* v_tail, int64_t tail_len, int64_t tail_cap,
                          const float* bias, int64_t bias_row_stride_t, int causal, void* out, int out_dtype, int64_t B, int Hq, int Hkv, int D,
                          int T, int elem_fmt, float scaling, void* workspace, int64_t workspace_bytes, void* stream) {
-    int ns = 0, gps = 0;
-    const int rc = multi_plan(B, Hq, Hkv, D, T, S_packed, tail_len, &ns, &gps);
+    AttnPlan p;
+    const int rc = multi_plan(B, Hq, Hkv, D, T, S_packed, tail_len, &p);
     if (rc != MSQ_OK) return rc;
+    const int ns = p.nsplit;
     const int64_t len = S_packed + tail_len;
-    if (elem_fmt != MSQ_FMT_FP8_E4M3 && elem_fmt != MSQ_FMT_FP4_E2M1) return kvm_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_multi: elem_fmt must be fp8_e4m3 or fp4_e2m1");
-    if (q_dtype != 1 && q_dtype != 2) return kvm_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_multi: q and the tail must be f16 (1) or bf16 (2)");
-    if (out_dtype != 0 && out_dtype != q_dtype) return kvm_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_multi: out must be float32 or the q dtype");
-    if (S_cap < 0 || S_cap % 32 || S_packed > S_cap) return kvm_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: S_packed exceeds S_cap (a multiple of 32)");
-    if (tail_len > tail_cap) return kvm_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: tail_len exceeds tail_cap");
-    if (bias && bias_row_stride_t != 0 && bias_row_stride_t < len)
-        return kvm_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: bias_row_stride_t must be 0 (rows [B, len]) or at least len (rows [B, T, stride])");
-    if (!q || !out || !workspace) return kvm_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: null buffer");
-    if (S_packed && (!k_codes || !k_scales || !v_codes || !v_scales)) return kvm_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: null buffer (planes)");
-    if (tail_len && (!k_tail || !v_tail)) return kvm_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: null buffer (tail)");
-    const int64_t need = B * Hq * (int64_t)T * ns * (D + 2) * (int64_t)sizeof(float);
-    if (workspace_bytes < need) return kvm_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: workspace too small (msq_kv_mx_attn_multi_workspace_bytes)");
-    if ((((uintptr_t)q | (uintptr_t)k_codes | (uintptr_t)k_scales | (uintptr_t)v_codes | (uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)workspace) & 15) != 0)
-        return kvm_fail(MSQ_ERR_BAD_ARG, "msq_kv_mx_attn_multi: buffers must be 16-byte aligned");      // v_scales, bias and out are read / written one element at a time
+    MultiArgs A;
+    set_attn_buffers(A, q, k_codes, k_scales, v_codes, v_scales, k_tail, v_tail, bias, workspace);
+    const char* own = (S_cap < 0 || S_cap % 32 || S_packed > S_cap) ? "S_packed exceeds S_cap (a multiple of 32)"
+                    : tail_len > tail_cap ? "tail_len exceeds tail_cap"
+                    : (bias && bias_row_stride_t != 0 && bias_row_stride_t < len) ? "bias_row_stride_t must be 0 (rows [B, len]) or at least len (rows [B, T, stride])"
+                    : nullptr;
+    const int bad = check_attn_common("msq_kv_mx_attn_multi", A, out, nullptr, elem_fmt, q_dtype, out_dtype, own, S_packed != 0, tail_len != 0, workspace_bytes,
+                                      B * Hq * (int64_t)T * ns * (D + 2) * (int64_t)sizeof(float), "workspace too small (msq_kv_mx_attn_multi_workspace_bytes)");
+    if (bad != MSQ_OK) return bad;
     const int G = Hq / Hkv, nrows = T * G;
     const int nr = nrows <= 16 ? 1 : (nrows <= 32 ? 2 : 4);          // 16-row tiles of a block: at most 64 rows per row tile
     const int ntiles = (nrows + nr * 16 - 1) / (nr * 16);
-    if ((int64_t)Hkv * ntiles > 65535) return kvm_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_multi: sizes beyond the launch grid");
-    if (B * Hq * (int64_t)T > 0x7FFFFFFF) return kvm_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_multi: sizes beyond the launch grid");
-    MultiArgs A;
-    A.q = q; A.kc = (const uint8_t*)k_codes; A.ks = (const uint8_t*)k_scales; A.vc = (const uint8_t*)v_codes; A.vs = (const uint8_t*)v_scales;
-    A.kt = k_tail; A.vt = v_tail; A.bias = bias; A.ws = (float*)workspace;
-    A.Hq = Hq; A.G = G; A.T = T; A.nsplit = ns; A.gps = gps; A.S_packed = (int)S_packed; A.tail_len = (int)tail_len; A.tail_cap = (int)tail_cap;
+    if ((int64_t)Hkv * ntiles > 65535) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_multi: sizes beyond the launch grid");
+    if (B * Hq * (int64_t)T > 0x7FFFFFFF) return kvp_fail(MSQ_ERR_UNSUPPORTED, "msq_kv_mx_attn_multi: sizes beyond the launch grid");
+    A.Hq = Hq; A.G = G; A.T = T; A.nsplit = ns; A.gps = p.gps; A.S_packed = (int)S_packed; A.tail_len = (int)tail_len; A.tail_cap = (int)tail_cap;
     A.ntiles = ntiles; A.causal = causal ? 1 : 0;
     A.S_cap = S_cap; A.bias_tstride = bias ? bias_row_stride_t : 0; A.bias_bstride = bias_row_stride_t ? (int64_t)T * bias_row_stride_t : len;
     A.scaling = scaling;
@@ -478,14 +412,14 @@ int msq_kv_mx_attn_multi(const void* q, int q_dtype, const void* k_codes, const 
 #undef MSQ_KVM_Q
 #undef MSQ_KVM_N
 #undef MSQ_KVM
-    if (hipGetLastError() != hipSuccess) return kvm_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_attn_multi: launch failed");
+    if (hipGetLastError() != hipSuccess) return kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_attn_multi: launch failed");
     const dim3 cgrid((unsigned)(B * Hq * T));
-#define MSQ_KVMC1(DV, OD) hipLaunchKernelGGL((k_kvp_attn_multi_combine<DV, OD>), cgrid, dim3(DV), 0, st, (const float*)workspace, out, ns)
+#define MSQ_KVMC1(DV, OD) hipLaunchKernelGGL((k_kvp_attn_combine<DV, OD>), cgrid, dim3(DV), 0, st, (const float*)workspace, out, ns, (const int*)nullptr, (int64_t)0)
 #define MSQ_KVMC(DV) do { if (out_dtype == 0) MSQ_KVMC1(DV, 0); else if (out_dtype == 1) MSQ_KVMC1(DV, 1); else MSQ_KVMC1(DV, 2); } while (0)
     if (D == 64) MSQ_KVMC(64); else MSQ_KVMC(128);
 #undef MSQ_KVMC
 #undef MSQ_KVMC1
-    return hipGetLastError() == hipSuccess ? MSQ_OK : kvm_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_attn_multi: launch failed");
+    return hipGetLastError() == hipSuccess ? MSQ_OK : kvp_fail(MSQ_ERR_LAUNCH, "msq_kv_mx_attn_multi: launch failed");
 }
 
 }  // extern "C"

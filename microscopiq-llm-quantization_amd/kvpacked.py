@@ -88,6 +88,29 @@ def _status(status, who):
         raise MsqError(who + ": MSQ_STATUS_NAN (a block holds Inf / NaN)")
 
 
+def _check_gap(who, gap):
+    if gap <= 0 or gap % GROUP:
+        raise MsqError(who + ": gap must be a positive multiple of 32")
+
+
+def _status_names(status):
+    """the bits of a state's status word by name"""
+    names = [n for bit, n in ((STATUS_OVERFLOW, "MSQ_STATUS_OVERFLOW"), (STATUS_NAN, "MSQ_STATUS_NAN")) if status & bit]
+    if status & ~(STATUS_OVERFLOW | STATUS_NAN):
+        names.append("status %d" % status)
+    return names
+
+
+def _step_lengths(p, t, n, S_cap, gap):
+    """(packed_len, tail_len, taken) after n single-token appends to a cache at (p, t): the rule of PackedKV.append in closed form.  A cache
+    holds S_cap packed tokens + a full tail and stays there: taken < n tells that it filled up."""
+    taken = max(0, min(n, S_cap + gap - (p + t)))
+    if taken > 0:
+        flushes = (t + taken - 1) // gap
+        p, t = p + flushes * gap, t + taken - flushes * gap
+    return p, t, taken
+
+
 def mx_pack(x, codes, scales, pos, elem_format, along_tokens, check_status=False):
     """x [B, H, T, D] (f32 / f16 / bf16) -> tokens pos .. pos + T of a code plane and its scale plane (in place).  T % 32 == 0,
     pos % 32 == 0.  along_tokens: the K form (blocks of 32 tokens of a channel), else the V form (blocks of 32 channels of a token)."""
@@ -124,8 +147,7 @@ class PackedKV:
     is packed first, then the token joins the tail."""
 
     def __init__(self, B, Hkv, D, dtype, elem_format="fp8_e4m3", gap=32, capacity=256, device="cuda"):
-        if gap <= 0 or gap % GROUP:
-            raise MsqError("PackedKV: gap must be a positive multiple of 32")
+        _check_gap("PackedKV", gap)
         if dtype not in (torch.float16, torch.bfloat16):
             raise MsqError("PackedKV: the cache dtype must be float16 or bfloat16")
         self.fmt_id = _fmt_id(elem_format)
@@ -166,6 +188,12 @@ class PackedKV:
     def _pack(self, k, v, pos):
         mx_pack(k, self.planes["k_codes"], self.planes["k_scales"], pos, self.elem_format, True)
         mx_pack(v, self.planes["v_codes"], self.planes["v_scales"], pos, self.elem_format, False)
+
+    def _unpack(self, pos, T):
+        """K and V of the packed tokens pos .. pos + T in the cache dtype"""
+        k = mx_unpack(self.planes["k_codes"], self.planes["k_scales"], pos, T, self.D, self.dtype, self.elem_format, True)
+        v = mx_unpack(self.planes["v_codes"], self.planes["v_scales"], pos, T, self.D, self.dtype, self.elem_format, False)
+        return k, v
 
     def _tail_put(self, k, v, at):
         n = k.shape[2]
@@ -221,37 +249,40 @@ class PackedKV:
 
     def dequantize(self):
         """K and V as [B, Hkv, len, D] in the cache dtype: the unpacked part followed by the tail."""
-        P = self.packed_len
         tk, tv = self._tail_get()
-        if P == 0:
+        if self.packed_len == 0:
             return tk.clone(), tv.clone()
-        k = mx_unpack(self.planes["k_codes"], self.planes["k_scales"], 0, P, self.D, self.dtype, self.elem_format, True)
-        v = mx_unpack(self.planes["v_codes"], self.planes["v_scales"], 0, P, self.D, self.dtype, self.elem_format, False)
+        k, v = self._unpack(0, self.packed_len)
         if self.tail_len:
             k, v = torch.cat([k, tk], dim=2), torch.cat([v, tv], dim=2)
         return k, v
+
+    def _prep_q(self, who, q, ndim, out_dtype, scaling):
+        """what the attention entries do with q before anything else: q [B, Hq, D] (ndim 3; [B, Hq, 1, D] is taken too) or [B, Hq, T, D]
+        (ndim 4) in the cache dtype -> (q contiguous and 16-byte aligned, out_dtype, scaling) with their defaults filled in"""
+        if ndim == 3 and q.ndim == 4 and q.shape[2] == 1:
+            q = q[:, :, 0, :]
+        if q.ndim != ndim or q.shape[0] != self.B or q.shape[-1] != self.D or q.dtype != self.dtype:
+            raise MsqError("%s: expected q [%d, Hq, %s%d] of %s" % (who, self.B, "T, " if ndim == 4 else "", self.D, self.dtype))
+        out_dtype = q.dtype if out_dtype is None else out_dtype
+        if out_dtype not in (q.dtype, torch.float32):
+            raise MsqError(who + ": out_dtype must be the q dtype or float32")
+        q = q.contiguous()
+        if q.data_ptr() % 16:
+            q = q.clone()
+        return q, out_dtype, float(self.D) ** -0.5 if scaling is None else float(scaling)
 
     def attend(self, q, bias=None, scaling=None, out_dtype=None):
         """softmax(scaling q K^T + bias) V for one query token per sequence, over the codes and the tail (the fused kernel).
         q [B, Hq, D] (or [B, Hq, 1, D]) in the cache dtype; bias [B, len] float32 (may hold -inf) or None; returns [B, Hq, D] in
         out_dtype (the q dtype or float32)."""
         _need_cuda(q, bias)
-        if q.ndim == 4 and q.shape[2] == 1:
-            q = q[:, :, 0, :]
-        if q.ndim != 3 or q.shape[0] != self.B or q.shape[2] != self.D or q.dtype != self.dtype:
-            raise MsqError("PackedKV.attend: expected q [%d, Hq, %d] of %s" % (self.B, self.D, self.dtype))
+        q, out_dtype, scaling = self._prep_q("PackedKV.attend", q, 3, out_dtype, scaling)
         Hq = q.shape[1]
-        out_dtype = q.dtype if out_dtype is None else out_dtype
-        if out_dtype not in (q.dtype, torch.float32):
-            raise MsqError("PackedKV.attend: out_dtype must be the q dtype or float32")
-        q = q.contiguous()
-        if q.data_ptr() % 16:
-            q = q.clone()
         if bias is not None:
             if tuple(bias.shape) != (self.B, self.len):
                 raise MsqError("PackedKV.attend: bias must be [%d, %d]" % (self.B, self.len))
             bias = bias.to(torch.float32).contiguous()
-        scaling = float(self.D) ** -0.5 if scaling is None else float(scaling)
         need = lib().msq_kv_mx_attn_workspace_bytes(self.B, Hq, self.Hkv, self.D, self.packed_len, self.tail_len)
         if need < 0:
             check(int(need), "msq_kv_mx_attn_workspace_bytes")
@@ -267,12 +298,6 @@ class PackedKV:
 
     def _capturing(self):
         return False
-
-    def _unpack(self, pos, T):
-        """K and V of the packed tokens pos .. pos + T in the cache dtype"""
-        k = mx_unpack(self.planes["k_codes"], self.planes["k_scales"], pos, T, self.D, self.dtype, self.elem_format, True)
-        v = mx_unpack(self.planes["v_codes"], self.planes["v_scales"], pos, T, self.D, self.dtype, self.elem_format, False)
-        return k, v
 
     def crop(self, n):
         """keep the first n tokens (0 <= n <= len): dequantize() of those is the same bits before and after.  n in the tail: tail_len
@@ -298,17 +323,13 @@ class PackedKV:
         codes and the tail (csrc/msq_kv_packed_multi.hip).  q [B, Hq, T, D] in the cache dtype; with causal, query t sees the positions
         <= len - T + t; bias float32 (may hold -inf) [B, len] (one row for every t) or [B, T, len], or None; returns [B, T, Hq, D] in
         out_dtype (the q dtype or float32).  A row whose every position is masked gives zeros."""
-        if q.ndim != 4 or q.shape[0] != self.B or q.shape[3] != self.D or q.dtype != self.dtype:
-            raise MsqError("PackedKV.attend_multi: expected q [%d, Hq, T, %d] of %s" % (self.B, self.D, self.dtype))
+        q, out_dtype, scaling = self._prep_q("PackedKV.attend_multi", q, 4, out_dtype, scaling)
         Hq, T = int(q.shape[1]), int(q.shape[2])
         if not 1 <= T <= MAX_QUERY_TOKENS:
             raise MsqError("PackedKV.attend_multi: 1 .. %d query tokens, not %d" % (MAX_QUERY_TOKENS, T))
         if T > self.len:
             raise MsqError("PackedKV.attend_multi: %d query tokens but the cache holds %d (append first: the query tokens are the cache's last T)"
                            % (T, self.len))
-        out_dtype = q.dtype if out_dtype is None else out_dtype
-        if out_dtype not in (q.dtype, torch.float32):
-            raise MsqError("PackedKV.attend_multi: out_dtype must be the q dtype or float32")
         stride_t = 0
         if bias is not None:
             if tuple(bias.shape) == (self.B, T, self.len):
@@ -318,12 +339,8 @@ class PackedKV:
         _need_cuda(q, bias)
         if self._capturing():
             raise MsqError("PackedKV.attend_multi runs on host lengths and cannot be captured")
-        q = q.contiguous()
-        if q.data_ptr() % 16:
-            q = q.clone()
         if bias is not None:
             bias = bias.to(torch.float32).contiguous()
-        scaling = float(self.D) ** -0.5 if scaling is None else float(scaling)
         need = lib().msq_kv_mx_attn_multi_workspace_bytes(self.B, Hq, self.Hkv, self.D, T, self.packed_len, self.tail_len)
         if need < 0:
             check(int(need), "msq_kv_mx_attn_multi_workspace_bytes")
@@ -371,8 +388,7 @@ class StaticPackedKV(PackedKV):
     _APPEND_ENTRY, _ATTN_ENTRY = "msq_kv_mx_append_dev", "msq_kv_mx_attn_decode_dev"      # SlotPackedKV: the _seq entries, the same arguments
 
     def __init__(self, B, Hkv, D, dtype, elem_format="fp8_e4m3", gap=32, max_len=256, device="cuda"):
-        if gap <= 0 or gap % GROUP:
-            raise MsqError("StaticPackedKV: gap must be a positive multiple of 32")
+        _check_gap("StaticPackedKV", gap)
         if max_len <= 0:
             raise MsqError("StaticPackedKV: max_len must be positive")
         self.S_cap = (int(max_len) + gap - 1) // gap * gap
@@ -422,16 +438,12 @@ class StaticPackedKV(PackedKV):
 
     # ---- the cache ------------------------------------------------------------------------------------------------------------------
     def _after_steps(self, n):
-        """the mirror's lengths after n single-token appends (the rule of PackedKV.append, in closed form)"""
-        if n <= 0:
-            return self.packed_len, self.tail_len
-        t = self.tail_len + n
-        flushes = (t - 1) // self.gap
-        packed = self.packed_len + flushes * self.gap
-        if packed > self.S_cap:
+        """the mirror's lengths after n single-token appends; raises when the cache cannot take all n"""
+        p, t, taken = _step_lengths(self.packed_len, self.tail_len, n, self.S_cap, self.gap)
+        if taken < n:
             raise MsqError("StaticPackedKV: %d more token(s) overflow the capacity of %d packed tokens (MSQ_STATUS_OVERFLOW on the device)"
                            % (n, self.S_cap))
-        return packed, t - flushes * self.gap
+        return p, t
 
     def advance_host(self, n=1):
         """apply n single-token steps to the host mirror (after n replays of a captured step); no device access"""
@@ -452,12 +464,15 @@ class StaticPackedKV(PackedKV):
         super().append(k, v)
         self._write_state()
 
-    def set_lengths(self, packed_len, tail_len):
-        """mirror and device state := (packed_len, tail_len), status cleared: restore after a warm-up, roll back"""
+    def _check_lengths(self, who, packed_len, tail_len):
         packed_len, tail_len = int(packed_len), int(tail_len)
         if packed_len < 0 or packed_len % self.gap or packed_len > self.S_cap or not 0 <= tail_len <= self.gap:
-            raise MsqError("StaticPackedKV.set_lengths: packed_len must be a multiple of gap within the capacity, tail_len within the tail")
-        self.packed_len, self.tail_len = packed_len, tail_len
+            raise MsqError(who + ".set_lengths: packed_len must be a multiple of gap within the capacity, tail_len within the tail")
+        return packed_len, tail_len
+
+    def set_lengths(self, packed_len, tail_len):
+        """mirror and device state := (packed_len, tail_len), status cleared: restore after a warm-up, roll back"""
+        self.packed_len, self.tail_len = self._check_lengths("StaticPackedKV", packed_len, tail_len)
         self._write_state(clear_status=True)
 
     def crop(self, n):
@@ -470,12 +485,9 @@ class StaticPackedKV(PackedKV):
         """read the device state back (one copy): the mirror takes its lengths; a status bit raises MsqError (set_lengths clears it)"""
         packed_len, tail_len, status, _ = self._read_state()
         self.packed_len, self.tail_len = int(packed_len), int(tail_len)
-        if status & STATUS_OVERFLOW:
-            raise MsqError("StaticPackedKV: MSQ_STATUS_OVERFLOW (an append found the cache full and dropped the token)")
-        if status & STATUS_NAN:
-            raise MsqError("StaticPackedKV: MSQ_STATUS_NAN (a packed block holds Inf / NaN)")
         if status:
-            raise MsqError("StaticPackedKV: status %d" % status)
+            raise MsqError("StaticPackedKV: " + " | ".join(_status_names(status)) + " (overflow: an append found the cache full and dropped the "
+                           "token; nan: a packed block holds Inf / NaN; set_lengths clears it)")
         return self.packed_len, self.tail_len
 
     def attend_dev(self, q, bias=None, scaling=None, out_dtype=None):
@@ -484,19 +496,9 @@ class StaticPackedKV(PackedKV):
         the length are never read; this is the form to capture), a narrower one must be [B, len] of the mirror and is copied into a buffer
         of that width first.  The workspace is allocated on the first call for a given Hq: run one eager call before capturing."""
         _need_cuda(q, bias)
-        if q.ndim == 4 and q.shape[2] == 1:
-            q = q[:, :, 0, :]
-        if q.ndim != 3 or q.shape[0] != self.B or q.shape[2] != self.D or q.dtype != self.dtype:
-            raise MsqError("StaticPackedKV.attend_dev: expected q [%d, Hq, %d] of %s" % (self.B, self.D, self.dtype))
+        q, out_dtype, scaling = self._prep_q("StaticPackedKV.attend_dev", q, 3, out_dtype, scaling)
         Hq = q.shape[1]
-        out_dtype = q.dtype if out_dtype is None else out_dtype
-        if out_dtype not in (q.dtype, torch.float32):
-            raise MsqError("StaticPackedKV.attend_dev: out_dtype must be the q dtype or float32")
         capturing = self._capturing()
-        if not q.is_contiguous() or q.data_ptr() % 16:
-            q = q.contiguous()
-            if q.data_ptr() % 16:
-                q = q.clone()
         width = self.S_cap + self.gap
         if bias is not None:
             if bias.ndim != 2 or bias.shape[0] != self.B:
@@ -513,7 +515,6 @@ class StaticPackedKV(PackedKV):
                     self._bias_pad = torch.zeros(self.B, width, dtype=torch.float32, device=self.device)
                 self._bias_pad[:, :bias.shape[1]] = bias
                 bias = self._bias_pad
-        scaling = float(self.D) ** -0.5 if scaling is None else float(scaling)
         ws = self._ws_dev.get(Hq)
         if ws is None:
             if capturing:
@@ -608,12 +609,8 @@ class SlotPackedKV(StaticPackedKV):
 
     def _slot_after(self, slot, n):
         """(lengths of the slot after n single-token steps, does it take all n): a slot holds S_cap packed tokens + a full tail and stays there"""
-        p, t = self._lens[slot]
-        fits = min(n, self.S_cap + self.gap - (p + t))
-        if fits > 0:
-            flushes = (t + fits - 1) // self.gap
-            p, t = p + flushes * self.gap, t + fits - flushes * self.gap
-        return (p, t), fits == n
+        p, t, taken = _step_lengths(*self._lens[slot], n, self.S_cap, self.gap)
+        return (p, t), taken == n
 
     def _steps(self, n, who):
         live = [b for b in range(self.B) if not self._idle[b]]
@@ -672,11 +669,9 @@ class SlotPackedKV(StaticPackedKV):
 
     def set_lengths(self, slot, packed_len, tail_len):
         """mirror and state row of one slot := (packed_len, tail_len), status cleared: restore after a warm-up, roll back"""
-        slot, packed_len, tail_len = self._slot(slot), int(packed_len), int(tail_len)
+        slot = self._slot(slot)
         self._host_only("set_lengths")
-        if packed_len < 0 or packed_len % self.gap or packed_len > self.S_cap or not 0 <= tail_len <= self.gap:
-            raise MsqError("SlotPackedKV.set_lengths: packed_len must be a multiple of gap within the capacity, tail_len within the tail")
-        self._lens[slot] = (packed_len, tail_len)
+        self._lens[slot] = self._check_lengths("SlotPackedKV", packed_len, tail_len)
         self._write_row(slot, "all")
 
     def crop(self, slot, n):
@@ -702,13 +697,7 @@ class SlotPackedKV(StaticPackedKV):
         statuses = [int(r[2]) for r in rows]
         if not raise_on_status:
             return self.lengths, statuses
-        bad = []
-        for b, st in enumerate(statuses):
-            names = [n for bit, n in ((STATUS_OVERFLOW, "MSQ_STATUS_OVERFLOW"), (STATUS_NAN, "MSQ_STATUS_NAN")) if st & bit]
-            if st & ~(STATUS_OVERFLOW | STATUS_NAN):
-                names.append("status %d" % st)
-            if names:
-                bad.append("slot %d: %s" % (b, " | ".join(names)))
+        bad = ["slot %d: %s" % (b, " | ".join(_status_names(st))) for b, st in enumerate(statuses) if st]
         if bad:
             raise MsqError("SlotPackedKV: " + "; ".join(bad) + " (overflow: an append found the slot full and dropped its token; nan: a packed "
                            "block holds Inf / NaN; reset(slot) clears it)")
@@ -810,8 +799,7 @@ def PackedMXKVCache(num_layers, elem_format="fp8_e4m3", gap=32, capacity=256, ma
     from transformers.cache_utils import Cache
     layer_cls = _make_layer_class()
     _fmt_id(elem_format)
-    if gap <= 0 or gap % GROUP:
-        raise MsqError("PackedMXKVCache: gap must be a positive multiple of 32")
+    _check_gap("PackedMXKVCache", gap)
     if max_len is not None and max_len <= 0:
         raise MsqError("PackedMXKVCache: max_len must be positive")
     return Cache(layers=[layer_cls(elem_format, gap, capacity, max_len) for _ in range(num_layers)])
@@ -845,13 +833,7 @@ def _packed_attention_forward(module, query, key, value, attention_mask, dropout
     if attention_mask is not None:
         if attention_mask.ndim != 4 or attention_mask.shape[1] != 1 or attention_mask.shape[2] != 1:
             raise MsqError("msq_packed_kv: expected a [B, 1, 1, S] attention mask at query length 1")
-        am = attention_mask[:, 0, 0, :]
-        if am.dtype == torch.bool:                               # the sdpa mask convention: True = attend
-            bias = torch.zeros(am.shape, dtype=torch.float32, device=am.device).masked_fill_(~am, float("-inf"))
-        else:
-            bias = am.to(torch.float32)
-        if bias.shape[0] != query.shape[0]:
-            bias = bias.expand(query.shape[0], -1)
+        bias = _mask_bias(attention_mask[:, 0, 0, :], query.shape[0])
     if isinstance(layer.packed, StaticPackedKV):                 # lengths from the device state; bias_stride = the mask length
         out = layer.packed.attend_dev(query[:, :, 0, :], bias, scaling)
     else:

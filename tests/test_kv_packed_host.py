@@ -6,14 +6,10 @@ import ctypes as C
 import pytest
 import torch
 
+from kv_packed_stubs import _msq, _tokens, dynamic_stub as _stub
+
 FP8, FP4 = 5, 8
 BAD_ARG, UNSUPPORTED = -1, -2
-
-
-def _msq():
-    import msq
-    msq._lib.lib()
-    return msq
 
 
 @pytest.mark.parametrize("fmt,code_bits", [("fp8_e4m3", 8), ("fp4_e2m1", 4)])
@@ -108,34 +104,6 @@ def test_pack_and_unpack_argument_errors():
         ("fmt", FP4), ("along", 0), ("stream", None))])
     assert unpack(D=48) == UNSUPPORTED and unpack(pos=100) == BAD_ARG and unpack(T=0) == 0
     assert unpack() == BAD_ARG and b"null buffer" in lib.msq_last_error()
-
-
-def _stub(gap=32):
-    kp = _msq().kvpacked
-
-    class Stub(kp.PackedKV):
-        """storage on the host and a log instead of launches: the timing rule is plain Python"""
-        def _check_device(self):
-            pass
-
-        def _reserve(self, need):
-            self.capacity = max(self.capacity, (need + 31) // 32 * 32)
-
-        def _check_kv(self, k, v):
-            pass
-
-        def _pack(self, k, v, pos):
-            assert k.shape == v.shape and k.shape[2] % 32 == 0 and pos % 32 == 0 and pos + k.shape[2] <= self.capacity
-            self.log.append((pos, k[0, 0, :, 0].tolist()))
-
-    s = Stub(1, 1, 32, torch.float16, "fp8_e4m3", gap=gap, capacity=32, device="cpu")
-    s.log = []
-    return s
-
-
-def _tokens(a, b):
-    t = torch.arange(a, b, dtype=torch.float16).reshape(1, 1, -1, 1).expand(1, 1, b - a, 32).contiguous()
-    return t, t.clone()
 
 
 def test_timing_rule_prefill_70_then_30_tokens():

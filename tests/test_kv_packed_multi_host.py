@@ -6,14 +6,18 @@ import ctypes as C
 import pytest
 import torch
 
+from kv_packed_stubs import _msq, _tokens, dynamic_stub, static_stub
+
 FP8, FP4 = 5, 8
 BAD_ARG, UNSUPPORTED = -1, -2
 
 
-def _msq():
-    import msq
-    msq._lib.lib()
-    return msq
+def _dynamic_stub(gap):
+    return dynamic_stub(gap, keep_tokens=True)                   # _pack keeps the tokens it is given so that _unpack can hand them back
+
+
+def _static_stub(gap, max_len):
+    return static_stub(gap, max_len, keep_tokens=True)
 
 
 def test_workspace_is_the_plan_times_the_query_tokens():
@@ -52,80 +56,6 @@ def test_c_entry_argument_errors_before_any_launch():
     assert call() == BAD_ARG and b"null buffer" in lib.msq_last_error()               # every size is fine: the buffers are looked at last
     assert lib.msq_kv_mx_attn_multi_workspace_bytes(2, 8, 2, 128, 0, 64, 3) == BAD_ARG
     assert lib.msq_kv_mx_attn_multi_workspace_bytes(2, 32, 2, 128, 4, 64, 3) == UNSUPPORTED
-
-
-def _dynamic_stub(gap):
-    kp = _msq().kvpacked
-
-    class Stub(kp.PackedKV):
-        """storage on the host; _pack keeps the tokens it is given so that _unpack can hand them back"""
-        def _check_device(self):
-            pass
-
-        def _reserve(self, need):
-            self.capacity = max(self.capacity, (need + 31) // 32 * 32)
-
-        def _check_kv(self, k, v):
-            pass
-
-        def _pack(self, k, v, pos):
-            assert k.shape == v.shape and k.shape[2] % 32 == 0 and pos % 32 == 0 and pos + k.shape[2] <= self.capacity
-            self.log.append((pos, k[0, 0, :, 0].tolist()))
-            for i in range(k.shape[2]):
-                self.store[pos + i] = (k[:, :, i].clone(), v[:, :, i].clone())
-
-        def _unpack(self, pos, T):
-            self.unpacks.append((pos, T))
-            return (torch.stack([self.store[pos + i][0] for i in range(T)], dim=2), torch.stack([self.store[pos + i][1] for i in range(T)], dim=2))
-
-    s = Stub(1, 1, 32, torch.float16, "fp8_e4m3", gap=gap, capacity=32, device="cpu")
-    s.log, s.store, s.unpacks = [], {}, []
-    return s
-
-
-def _static_stub(gap, max_len):
-    kp = _msq().kvpacked
-
-    class Stub(kp.StaticPackedKV):
-        def _check_device(self):
-            pass
-
-        def _alloc_planes(self):
-            self.planes, self.capacity = {}, self.S_cap
-
-        def _alloc_state(self):
-            self.dev, self.writes, self.capturing = [0, 0, 0, 0], 0, False
-
-        def _write_state(self, clear_status=False):
-            self.dev[:2] = [self.packed_len, self.tail_len]
-            if clear_status:
-                self.dev[2] = 0
-            self.writes += 1
-
-        def _read_state(self):
-            return list(self.dev)
-
-        def _capturing(self):
-            return self.capturing
-
-        def _check_kv(self, k, v):
-            pass
-
-        def _pack(self, k, v, pos):
-            for i in range(k.shape[2]):
-                self.store[pos + i] = (k[:, :, i].clone(), v[:, :, i].clone())
-
-        def _unpack(self, pos, T):
-            return (torch.stack([self.store[pos + i][0] for i in range(T)], dim=2), torch.stack([self.store[pos + i][1] for i in range(T)], dim=2))
-
-    s = Stub(1, 1, 32, torch.float16, "fp8_e4m3", gap=gap, max_len=max_len, device="cpu")
-    s.store = {}
-    return s
-
-
-def _tokens(a, b):
-    t = torch.arange(a, b, dtype=torch.float16).reshape(1, 1, -1, 1).expand(1, 1, b - a, 32).contiguous()
-    return t, t.clone()
 
 
 def _tail(s):

@@ -4,16 +4,12 @@ is a list of rows moved by the rule of include/msq.h (as in test_kv_packed_stati
 import pytest
 import torch
 
+from kv_packed_stubs import _msq, _tokens, dynamic_stub as _dynamic_stub
+
 FP8, FP4 = 5, 8
 BAD_ARG, UNSUPPORTED = -1, -2
 PTR = 4096                                                       # a non-null, 16-byte aligned "pointer" for entries that return before they look
 OVERFLOW, NAN, IDLE = 8, 1, 1
-
-
-def _msq():
-    import msq
-    msq._lib.lib()
-    return msq
 
 
 def test_append_seq_and_decode_seq_argument_errors():
@@ -61,27 +57,6 @@ def test_append_seq_and_decode_seq_argument_errors():
 # ---------------------------------------------------------------------------------------------------------------------
 # the per-slot mirror, on stubs
 # ---------------------------------------------------------------------------------------------------------------------
-def _dynamic_stub(gap):
-    kp = _msq().kvpacked
-
-    class Stub(kp.PackedKV):
-        def _check_device(self):
-            pass
-
-        def _reserve(self, need):
-            self.capacity = max(self.capacity, (need + 31) // 32 * 32)
-
-        def _check_kv(self, k, v):
-            pass
-
-        def _pack(self, k, v, pos):
-            self.log.append((pos, k[0, 0, :, 0].tolist()))
-
-    s = Stub(1, 1, 32, torch.float16, "fp8_e4m3", gap=gap, capacity=32, device="cpu")
-    s.log = []
-    return s
-
-
 def _slot_stub(B, gap, max_len):
     kp = _msq().kvpacked
 
@@ -150,11 +125,6 @@ def _slot_stub(B, gap, max_len):
     s = Stub(B, 1, 32, torch.float16, "fp8_e4m3", gap=gap, max_len=max_len, device="cpu")
     s.log = [[] for _ in range(B)]
     return s
-
-
-def _tokens(a, b):
-    t = torch.arange(a, b, dtype=torch.float16).reshape(1, 1, -1, 1).expand(1, 1, b - a, 32).contiguous()
-    return t, t.clone()
 
 
 def _step_tokens(values):

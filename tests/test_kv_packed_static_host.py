@@ -6,15 +6,11 @@ import ctypes as C
 import pytest
 import torch
 
+from kv_packed_stubs import _msq, _tokens, dynamic_stub as _dynamic_stub, static_stub as _static_stub
+
 FP8, FP4 = 5, 8
 BAD_ARG, UNSUPPORTED = -1, -2
 PTR = 4096                                                       # a non-null, 16-byte aligned "pointer" for entries that return before they look
-
-
-def _msq():
-    import msq
-    msq._lib.lib()
-    return msq
 
 
 def _plan_splits(lib, B, Hq, Hkv, D, S):
@@ -103,84 +99,6 @@ def test_append_dev_and_decode_dev_argument_errors():
 # ---------------------------------------------------------------------------------------------------------------------
 # the host mirror, on stubs
 # ---------------------------------------------------------------------------------------------------------------------
-def _dynamic_stub(gap):
-    kp = _msq().kvpacked
-
-    class Stub(kp.PackedKV):
-        def _check_device(self):
-            pass
-
-        def _reserve(self, need):
-            self.capacity = max(self.capacity, (need + 31) // 32 * 32)
-
-        def _check_kv(self, k, v):
-            pass
-
-        def _pack(self, k, v, pos):
-            self.log.append((pos, k[0, 0, :, 0].tolist()))
-
-    s = Stub(1, 1, 32, torch.float16, "fp8_e4m3", gap=gap, capacity=32, device="cpu")
-    s.log = []
-    return s
-
-
-def _static_stub(gap, max_len):
-    kp = _msq().kvpacked
-
-    class Stub(kp.StaticPackedKV):
-        """storage on the host; the device state is a list that _append_dev moves by the rule of include/msq.h (the kernels' side of the
-        contract, restated), so that sync() can be compared with the mirror"""
-        def _check_device(self):
-            pass
-
-        def _alloc_planes(self):
-            self.planes, self.capacity = {}, self.S_cap
-
-        def _alloc_state(self):
-            self.dev, self.writes, self.launches, self.capturing = [0, 0, 0, 0], 0, 0, False
-
-        def _write_state(self, clear_status=False):
-            self.dev[:2] = [self.packed_len, self.tail_len]
-            if clear_status:
-                self.dev[2] = 0
-            self.writes += 1
-
-        def _read_state(self):
-            return list(self.dev)
-
-        def _capturing(self):
-            return self.capturing
-
-        def _check_kv(self, k, v):
-            pass
-
-        def _pack(self, k, v, pos):
-            assert k.shape == v.shape and k.shape[2] % 32 == 0 and pos % 32 == 0 and pos + k.shape[2] <= self.capacity
-            self.log.append((pos, k[0, 0, :, 0].tolist()))
-
-        def _append_dev(self, k, v):
-            self.launches += 1
-            p, t = self.dev[:2]
-            if t == self.gap:
-                if p + self.gap > self.S_cap:
-                    self.dev[2] |= 8
-                    return
-                self.log.append((p, self.k_tail[0, 0, :, 0].tolist()))
-                p, t = p + self.gap, 0
-            self.k_tail[:, :, t:t + 1] = k
-            self.v_tail[:, :, t:t + 1] = v
-            self.dev[:2] = [p, t + 1]
-
-    s = Stub(1, 1, 32, torch.float16, "fp8_e4m3", gap=gap, max_len=max_len, device="cpu")
-    s.log = []
-    return s
-
-
-def _tokens(a, b):
-    t = torch.arange(a, b, dtype=torch.float16).reshape(1, 1, -1, 1).expand(1, 1, b - a, 32).contiguous()
-    return t, t.clone()
-
-
 def test_capacity_is_max_len_rounded_up_to_the_gap():
     for gap, max_len, cap in ((32, 256, 256), (32, 250, 256), (64, 130, 192), (64, 64, 64), (32, 1, 32)):
         s = _static_stub(gap, max_len)
