@@ -26,7 +26,21 @@ are the prerequisite for paging, not paging), a transformers Cache over SlotPack
 length), prefill attention over the codes (more than 32 query tokens go to sdpa on the dequantised tensors),
 MicroScopiQ outlier caches, a device-length or per-sequence form of attend_multi and a device-side multi-token append (both run on the host
 mirror's lengths and cannot be captured), capture of a whole transformers model (its mask and position plumbing is not ours: PackedMXKVCache(max_len=...)
-runs eagerly).  Every entry raises MsqError on CPU tensors: there is no CPU fallback."""
+runs eagerly).  Every entry raises MsqError on CPU tensors: there is no CPU fallback.
+
+Head dims: mx_pack / mx_unpack and PackedKV's append / dequantize / crop take every head_dim that is a multiple of 32 up to 256 (pack / unpack
+are pinned to the oracle at 32, 64, 96, 128, 160 and 256, the cache at 64, 96 and 256); the attention kernels exist for 64 and 128, and attend /
+attend_dev / attend_multi raise MsqError (head_dim must be 64 or 128) before any launch elsewhere.
+
+GPU tests (tests/test_gpu_f3_kv_packed*.py; DESIGN.md 5.013 maps kernel instantiations to tests):
+  test_gpu_f3_kv_packed.py           pack / unpack against the oracle, attend against float64 (gap 32, 2 or 8 query heads per kv head), a model
+  test_gpu_f3_kv_packed_static.py    attend_dev and the captured step, bit-equal to the host-length path; overflow, status
+  test_gpu_f3_kv_packed_multi.py     attend_multi against float64, row independence, crop, a model fed in chunks
+  test_gpu_f3_kv_packed_slots.py     ragged slots, slot reuse, idle slots, bit-equal to every slot's own cache
+  test_gpu_f3_kv_packed_coverage.py  1, 3, 4, 5, 6 and 7 query heads per kv head (1 and 3 kv heads), gap 64 / 96 (tail chunks after the first,
+                                     a full tail, the device flush of two K groups), an ALiBi bias with scaling != head_dim^-0.5, scale
+                                     bytes that differ between neighbours, blocks at the ends of the fp16 / bf16 range, head_dim 96 / 256,
+                                     the row-tile boundaries of attend_multi and T == len"""
 import ctypes as C
 
 import torch

@@ -1,6 +1,6 @@
 """SURVEY 8 row f3, the PACKED MX KV cache (msq.kvpacked, csrc/msq_kv_packed.hip).
 
-Pack / unpack: the planes decode to the float32 `_quantize_mx` values bit for bit (oracle and package), the V planes of an fp8 cache at
+Pack / unpack: the planes decode to the float32 `_quantize_mx` values bit for bit (oracle and package) at head_dim 32 .. 256, the V planes of an fp8 cache at
 head_dim 128 are the bytes of mx_pack_act, a pack touches only its own token range, a planted Inf raises MSQ_STATUS_NAN.
 Attention: float64 softmax attention over dequantize().double() -- the exact values the codes hold, so quantisation error is not in the
 comparison -- is the reference.  The float32 output may be off by at most 4 x the error of torch's float32 math-backend SDPA on the same
@@ -54,7 +54,7 @@ def _pack_inputs(T, D, along_tokens):
 
 @pytest.mark.parametrize("along_tokens", [1, 0])
 @pytest.mark.parametrize("fmt", FMTS)
-@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("D", [32, 64, 96, 128, 160, 256])
 def test_unpack_of_pack_is_quantize_mx_f32(msq, O, D, fmt, along_tokens):
     kp = msq.kvpacked
     T, S_cap = 64, 96
@@ -86,10 +86,11 @@ def test_v_planes_of_fp8_are_mx_pack_act_bytes(msq):
         assert torch.equal(P["v_codes"].reshape(-1, D), codes) and torch.equal(P["v_scales"].reshape(-1, D // 32), scales)
 
 
-@pytest.mark.parametrize("fmt", FMTS)
-def test_pack_touches_only_its_token_range(msq, fmt):
+# head_dim 64 keeps the ids it had before the other head dims were added
+@pytest.mark.parametrize("fmt,D", [pytest.param(f, d, id=f if d == 64 else "%s-D%d" % (f, d)) for d in (64, 32, 96, 256) for f in FMTS])
+def test_pack_touches_only_its_token_range(msq, fmt, D):
     kp = msq.kvpacked
-    D, S_cap, pos, T = 64, 160, 64, 32
+    S_cap, pos, T = 160, 64, 32
     x = _rand((B, HKV, T, D), 3, torch.bfloat16).to(dev())
     P = _planes(kp, B, HKV, S_cap, D, fmt, fill=0xA5)
     kp.mx_pack(x, P["k_codes"], P["k_scales"], pos, fmt, True)
